@@ -5,16 +5,19 @@ synthetic (B,48,2911,10) -> (B,12,2911,1) batches).
     python bench.py [--gpus N --steps K --warmup W]          # N > 1: starts N ranks itself (one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W                # or under torchrun: RANK / WORLD_SIZE come from the env
+    python bench.py --full                                    # + roofline, CPU baseline, parity, configs_extra
 
 A step = forward + HuberLoss + backward + (RCCL all-reduce of the flat 12.3 MB gradient, the per-rank parameter
 checksums riding in its tail) + clip(1.0) + AdamW + cosine-warm-restart scheduler, training mode (every dropout
 site active), inputs resident in HBM.  Weak scaling: every rank processes `--batch` (default 8) samples;
-value = all samples / max-over-ranks time.  Rank 0 prints ONE JSON line (< 4 KB: the driver parses the last stdout line)
-carrying `roofline` (dominant kernel, measured with events on the launch stream) and, at N=1, `cpu_baseline` (the CPU
-oracle's train step timed on the host cores of this box) and `configs_extra` (BASELINE configs[2] = bf16 and the
-configs[4] per-GPU shape L_in=96 / L_out=24, each with its roofline summary).  N > 1: `config.dist` carries the
-event-timed all-reduce (`allreduce_ms`).  Per-call-site GEMM tables, the non-GEMM block and per-rank lists go to
-`bench_detail.json` (--detail-json) next to this script.
+value = all samples / max-over-ranks time.  Rank 0 prints ONE JSON line (< 4 KB: the driver parses the last stdout line).
+A plain run sets up, warms up, times the --steps steps and prints that line; N > 1: `config.dist` carries the
+event-timed all-reduce (`allreduce_ms`).  --dump-outputs DIR writes what the last timed step computed as DIR/*.npy.
+--full adds, after the timed region, `roofline` (dominant kernel, measured with events on the launch stream) and,
+at N=1, `cpu_baseline` (the CPU oracle's train step timed on the host cores of this box), `parity` and `configs_extra`
+(BASELINE configs[2] = bf16 and the configs[4] per-GPU shape L_in=96 / L_out=24, each with its roofline summary, and
+the reference's loop body).  Per-call-site GEMM tables, the non-GEMM block and per-rank lists go to `bench_detail.json`
+(--detail-json) next to this script.
 """
 from __future__ import annotations
 
@@ -117,13 +120,15 @@ def compact_line(line: dict):
 
 
 def emit(line: dict, detail_path=None):
-    """Write the detail side file, then print the compact headline as the last stdout line."""
+    """Write the detail side file (when anything was cut from the headline), then print the compact headline as the last
+    stdout line."""
     head, detail = compact_line(line)
     path = detail_path or os.environ.get("TECM_BENCH_DETAIL", os.path.join(ROOT, "bench_detail.json"))
     try:
-        with open(path, "w") as f:
-            json.dump(detail, f, indent=1)
-        head["detail"] = os.path.relpath(path, ROOT) if path.startswith(ROOT) else path
+        if len(detail) > 1:                                # more than `headline_of`
+            with open(path, "w") as f:
+                json.dump(detail, f, indent=1)
+            head["detail"] = os.path.relpath(path, ROOT) if path.startswith(ROOT) else path
     except OSError as e:                                   # a read-only checkout must not cost the headline
         head["detail"] = f"not written: {e.__class__.__name__}"
     text = json.dumps(head)
@@ -146,14 +151,20 @@ def parse():
     ap.add_argument("--precision", choices=["fp32", "bf16", "bf16x3", "bf16x6"], default="fp32",
                     help="fp32 = BASELINE configs[1] (exact-f32 MFMA); bf16 = configs[2] (bf16 MFMA, fp32 accumulate)")
     ap.add_argument("--eval-mode", action="store_true", help="dropout off (diagnostics only)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure the roofline (per-GEMM timing pass) and, at N=1, the CPU "
+                         "baseline, parity and configs_extra; the --no-* flags below leave parts of it out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, trainable parameters, AdamW first moment) "
+                         "as DIR/<name>.npy, float32, at most 64 MB in all")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-batch", type=int, default=2, help="CPU baseline batch (BASELINE configs[0]: B=2)")
     ap.add_argument("--cpu-steps", type=int, default=3, help="timed CPU train steps after one warm-up step")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-other-precisions", action="store_true",
-                    help="skip configs_extra (the bf16 and L_in=96 legs that follow the main run at N=1 with default flags)")
+                    help="skip configs_extra (the bf16 and L_in=96 legs that follow the main run at N=1 with --full)")
     ap.add_argument("--emulation-modes", action="store_true",
-                    help="also time the opt-in bf16x6 / bf16x3 modes (context only; not part of the default run)")
+                    help="with --full, also time the opt-in bf16x6 / bf16x3 modes (context only)")
     ap.add_argument("--loop", choices=["native", "reference"], default="native",
                     help="native: tecmollm.train.TrainStep (flat buffers, fused clip + AdamW).  reference: the statements of "
                          "the reference's own loop body (train.py:57-112) around the drop-in model -- autocast(bf16), "
@@ -167,7 +178,12 @@ def parse():
                     help="fixed: one resident batch (default).  window: every step's batch is drawn by the device "
                          "window sampler (tecm_window_batch) from a resident synthetic series, as train.py:57-65 "
                          "draws it from the DataLoader")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.loop == "reference":
+        ap.error("--dump-outputs covers the native TrainStep path, not --loop reference")
+    return args
 
 
 # ------------------------------------------------------------------------------------------ N-rank launcher
@@ -662,6 +678,25 @@ class WindowFeed:
         return sum(a.elapsed_time(b) for a, b in self.events) / max(len(self.events), 1)
 
 
+DUMP_BUDGET = 64 * 10 ** 6       # bytes, all --dump-outputs files together
+
+
+def dump_outputs(out_dir: str, arrays: dict) -> None:
+    """DIR/<name>.npy (float32, flattened) per array.  An array longer than its even share of DUMP_BUDGET is replaced by a
+    fixed sample of that many elements (indices from a generator seeded 0, in ascending order), so that two builds
+    given the same arguments write comparable files.  The loss and the updated parameters are what a caller of the step
+    receives; the AdamW first moment carries the step's gradients at full scale, where the parameters only move by lr."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = (DUMP_BUDGET - 4096 * len(arrays)) // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().float().reshape(-1)
+        if a.numel() > share:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:share].sort().values
+            a = a[idx.to(a.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), a.cpu().numpy())
+
+
 def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -765,9 +800,12 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     check_device_errors(dev, sync=True)                # bad time indices / diverged ranks reported by any step
+    if args.dump_outputs and rank == 0:                # before the roofline pass below steps the model further
+        dump_outputs(args.dump_outputs, {"loss": loss, "trainable_params": ts.optimizer.flat_param,
+                                         "adamw_exp_avg": ts.optimizer.exp_avg})
     # the roofline's per-GEMM events are collected in a SEPARATE short pass: `value` above carries no event bracketing
     shape_agg = None
-    if not args.no_kernel_timing:                      # every rank runs it: the steps contain the collective
+    if args.full and not args.no_kernel_timing:        # every rank runs it: the steps contain the collective
         shape_agg = shape_pass(ts, lambda: batch(False), ei, ew)
     tmax = torch.tensor([dt], device=dev, dtype=torch.float64)
     step_ms = [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)]      # this rank's device time per step
@@ -826,11 +864,11 @@ def main():
             line["config"]["data_feed_share_of_step"] = round(d_ms / (dt / args.steps * 1e3), 5)
         if dist_info is not None:
             line["config"]["dist"] = dist_info
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"], ref = cpu_baseline(cfg, args)
             line["parity"] = rmse_vs_ref(cfg, args, dev, ref)
         default_shape = args.L_in == 48 and args.L_out == 12 and args.data == "fixed"
-        if world == 1 and args.precision == "fp32" and default_shape and not args.no_other_precisions:
+        if args.full and world == 1 and args.precision == "fp32" and default_shape and not args.no_other_precisions:
             # `value` above is the exact-fp32 number (BASELINE configs[1]).  Two more BASELINE configurations are
             # measured here, each with its own roofline: configs[2] (bf16 autocast semantics, same workload) and the
             # per-GPU shape of configs[4] (L_in = 96 / L_out = 24: twice the rows and tokens per sample), fp32.

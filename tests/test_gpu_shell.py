@@ -666,10 +666,9 @@ def test_reference_training_loop_body_runs_unchanged(dev):
     assert np.isfinite(total_loss) and torch.isfinite(after).all() and not torch.equal(before, after)
 
 def test_bench_default_command_prints_a_compact_parseable_last_line(dev, tmp_path):
-    """What the driver runs at round end: `python bench.py` with NO flags.  Its LAST stdout line must be one JSON object
-    under 4 KB (the driver keeps ~8 KB of stdout tail; round 4's 24 KB line was cut and recorded as parsed: null) with
-    the contract's keys, a scalar roofline summary, cpu_baseline, parity and both configs_extra legs; the per-shape tables
-    are in the side file."""
+    """`python bench.py --full` with no other flags.  Its LAST stdout line must be one JSON object under 4 KB (the driver
+    keeps ~8 KB of stdout tail; round 4's 24 KB line was cut and recorded as parsed: null) with the contract's keys, a
+    scalar roofline summary, cpu_baseline, parity and both configs_extra legs; the per-shape tables are in the side file."""
     import json
     import subprocess
     import sys
@@ -677,7 +676,8 @@ def test_bench_default_command_prints_a_compact_parseable_last_line(dev, tmp_pat
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", TECM_BENCH_DETAIL=str(tmp_path / "detail.json"))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py")], env=env, capture_output=True, text=True, timeout=1200)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full"], env=env, capture_output=True, text=True,
+                       timeout=1200)
     assert r.returncode == 0, r.stderr[-3000:]
     last = r.stdout.strip().splitlines()[-1]
     assert len(last) < 4096, len(last)
@@ -699,3 +699,39 @@ def test_bench_default_command_prints_a_compact_parseable_last_line(dev, tmp_pat
         assert e["samples_per_s"] > 0 and 0 < e["roofline"]["frac"] < 1 and "step" in e["roofline"]
     detail = json.load(open(tmp_path / "detail.json"))
     assert len(detail["roofline"]["shapes"]) >= 8 and detail["configs_extra"]["bf16"]["roofline"]["shapes"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_reproducible_outputs(dev, tmp_path):
+    """A plain `bench.py` run times exactly --steps steps and carries none of the --full legs; --dump-outputs writes what
+    the last timed step computed (loss, trainable parameters, AdamW first moment) as float32 .npy files under 64 MB, and a
+    second run with the same arguments starts from the same inputs and lands on the same values."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", TECM_BENCH_DETAIL=str(tmp_path / "detail.json"))
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--batch", "1",
+                            "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert len(line["config"]["step_ms_min_max"]) == 2
+        assert line["roofline"] is None and not {"cpu_baseline", "parity", "configs_extra", "detail"} & set(line)
+        files = sorted(p.name for p in out.iterdir())
+        assert files == ["adamw_exp_avg.npy", "loss.npy", "trainable_params.npy"], files
+        assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 10 ** 6
+        d = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in d.values())
+        assert d["loss"].shape == (1,) and d["trainable_params"].shape == d["adamw_exp_avg"].shape
+        dumps.append(d)
+    assert not (tmp_path / "detail.json").exists()          # nothing was cut from a plain headline
+    a, b = dumps
+    assert abs(a["loss"][0] - b["loss"][0]) <= 1e-4 * abs(a["loss"][0])
+    # three AdamW steps move a parameter by at most ~3 lr = 3e-4, whatever the rounding of its gradient
+    assert np.abs(a["trainable_params"] - b["trainable_params"]).max() < 1e-3
+    assert np.abs(a["adamw_exp_avg"] - b["adamw_exp_avg"]).max() <= 1e-3 * np.abs(a["adamw_exp_avg"]).max()

@@ -599,6 +599,24 @@ def test_bench_counts_gpus_from_sysfs_without_the_hip_runtime(tmp_path, monkeypa
     assert "torch.cuda" not in launcher                               # the parent never asks the runtime
 
 
+def test_bench_dump_outputs_keeps_small_arrays_whole_and_samples_large_ones_the_same_way(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per array within DUMP_BUDGET; an array over its share becomes a fixed sample, so that
+    two runs (two builds) write element-for-element comparable files."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 2 * 4096 + 2 * 4 * 1000)          # a share of 1000 float32 per array
+    big = torch.arange(5000, dtype=torch.float64)
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"loss": torch.tensor(0.5), "big": big})
+    a_big, b_big = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a_big.dtype == np.float32 and a_big.shape == (1000,) and np.array_equal(a_big, b_big)
+    assert np.all(np.diff(a_big) > 0) and len(np.unique(a_big)) == 1000     # distinct elements, in ascending order
+    loss = np.load(tmp_path / "a" / "loss.npy")
+    assert loss.dtype == np.float32 and loss.tolist() == [0.5]
+
+
 def test_isa_audit_of_hand_issued_lds_reads_catches_early_uses():
     """__graft_entry__.audit_hand_issued_lds_reads (run by build() on gemm_bf16_tn.hip's ISA): a register a hand-issued
     ds_read_b64_tr_b16 writes may not be touched before the counted s_waitcnt that retires it."""

@@ -9,7 +9,7 @@ OUT=$R/gpurun_out/prof_${TAG}_${PREC}
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 BENCH="python3 $R/bench.py --precision $PREC --no-cpu-baseline --no-other-precisions"
-rocprofv3 --kernel-trace --stats -d $OUT/stats -o p -- $BENCH --steps 3 --warmup 1 > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/stats -o p -- $BENCH --full --steps 3 --warmup 1 > $OUT/stats.log 2>&1
 echo "stats done"; grep -o '"value": [0-9.]*' $OUT/stats.log | head -1
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/fetch -o p -- $BENCH --steps 1 --warmup 1 --no-kernel-timing > $OUT/fetch.log 2>&1
 echo "fetch done"

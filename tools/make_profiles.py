@@ -4,7 +4,7 @@ under profiles/.
 
     python tools/make_profiles.py gpurun_out/prof_r02_fp32 r02 fp32
 
-<dir> holds stats/ (--kernel-trace --stats of `bench.py --steps 3 --warmup 1 --no-cpu-baseline`) with stats.log,
+<dir> holds stats/ (--kernel-trace --stats of `bench.py --full --steps 3 --warmup 1 --no-cpu-baseline`) with stats.log,
 fetch/ and write/ (--pmc FETCH_SIZE / WRITE_SIZE passes) and mfma/ (--pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE),
 each collected in its own run as MI355X_MICROARCH.md prescribes; every pass is a rocpd SQLite database (p_results.db).
 gfx950 corrections of the guide's HBM section: the counters are in KiB; FETCH_SIZE reports half of the bytes of wide
@@ -74,7 +74,7 @@ def main():
     if "adamw_kernel" in ks:             # one optimizer launch per step: counts the steps of bench.py's per-shape GEMM timing pass
         steps = ks["adamw_kernel"][0]    # (3 more after the timed region) as well
     tot = sum(v[1] for v in ks.values())
-    out = [f"# Round {tag[1:]} -- rocprofv3 --kernel-trace --stats of `python3 bench.py --precision {prec} --steps {j['steps']} "
+    out = [f"# Round {tag[1:]} -- rocprofv3 --kernel-trace --stats of `python3 bench.py --full --precision {prec} --steps {j['steps']} "
            f"--warmup {j['warmup']} --no-cpu-baseline --no-other-precisions`\n",
            f"B={B}, {prec} (BASELINE configs[{2 if prec == 'bf16' else 1}]), GATv2 per_timestep, dropout on; {steps} steps in the "
            f"trace; bench line of the same run: {j['value']} samples/s, {j['ms_per_step']} ms/step, `roofline.kernel = "

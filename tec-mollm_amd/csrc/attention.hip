@@ -272,7 +272,12 @@ __device__ __forceinline__ void attention_bwd_body(const float* __restrict__ qkv
 // then returns NON-REPRODUCIBLE garbage from T = 16 on, dropout on or off (tools/scratch/att_debug.py: three launches,
 // three answers; T = 13 fine), while the identical source with the hash behind a call is exact and bit-reproducible at every
 // T.  The body sits at the edge of the 512-register file by design (see above); which side of that edge the allocator
-// lands on must not depend on an inlining decision, so the call is spelled out.  test_attention_fwd_bwd[13..32] is the guard.
+// lands on must not depend on an inlining decision, so the call is spelled out.  The allocation has moved since: hipcc now
+// spills 92 VGPRs for the fp32 instance (240 bytes/lane of scratch) and 18 for the bf16-qkv ones (Q16, Q16 + D16; 80
+// bytes/lane), and that allocation is verified at every T, every instance, dropout on and off
+// (tests/test_gpu_ops.py::test_attention_every_t_matches_float64) and bit-reproducible over three launches of a 600-block
+// grid into NaN-filled outputs (::test_attention_bwd_qstream_reproducible).  Those counts are the ceilings of build()
+// (__graft_entry__.py, SPILL_CEILINGS): an allocation that spills more fails the build until the tests have seen it.
 __device__ __attribute__((noinline)) float att_drop_mult_call(uint64_t seed, uint64_t idx, uint32_t thresh, float inv_keep) {
   return tecm_drop_mult(seed, idx, thresh, inv_keep);
 }

@@ -287,6 +287,52 @@ def compare_forward_backward(cfg: dict, B: int, grid: Tuple[int, int], threshold
     return res
 
 
+def batch_vs_single_sample_grads(cfg: dict, B: int, grid: Tuple[int, int], seed: int, precision: str = "fp32",
+                                 device: str = "cuda") -> Dict[str, Tuple[float, float]]:
+    """Eval-mode gradients of ONE B-sample step (Huber, mean) against the mean of the B single-sample steps' gradients of
+    the same model on the same samples (accumulated in float64): {trainable tensor: (max-norm rel, elem_err(rtol=1e-4,
+    atol_rms=1e-5))}.  The mean loss of the batch is the mean of the per-sample losses, the forward is per-sample
+    bit-exact, and the batch's loss gradient is the single-sample one times 1/B (a power of two for B = 8, so it commutes
+    with every bf16 rounding): what may differ is the fp32 summation order of the reductions over rows -- weight
+    gradients, split-K slabs, partial rows of the spatial stage and its atomics -- and every shape-keyed choice the batch
+    makes (tile heights, split-K counts, graph chunks) that the single-sample step, checked against the oracle, does not."""
+    N = grid[0] * grid[1]
+    assert N == cfg["num_nodes"]
+    L = cfg["temporal_seq_len"]
+    model = build_model(cfg, R.init_params(cfg, seed=seed), device, "per_timestep", precision=precision).eval()
+    x, tf, y = R.synthetic_batch(B, L, N, cfg["spatial_in_channels_base"], cfg["prediction_horizon"], seed=seed + 100)
+    ei = R.grid_graph(grid[0], grid[1])[0].to(device)
+    xd, yd = x.to(device), y.to(device)
+    tfd = tf[:, :, 0, :].contiguous().to(device).unsqueeze(-2).expand(B, L, N, 4)
+
+    def grads(b0, b1):
+        model.zero_grad(set_to_none=True)
+        torch.nn.functional.huber_loss(model(xd[b0:b1], tfd[b0:b1], ei), yd[b0:b1]).backward()
+        return {k: p.grad for k, p in model.named_parameters() if p.grad is not None}
+    batch = {k: g.clone() for k, g in grads(0, B).items()}
+    acc = {k: torch.zeros_like(g, dtype=torch.float64) for k, g in batch.items()}
+    for b in range(B):
+        one = grads(b, b + 1)
+        assert one.keys() == acc.keys(), sorted(one.keys() ^ acc.keys())
+        for k, g in one.items():
+            acc[k] += g.double()
+    model.zero_grad(set_to_none=True)
+    assert all(torch.isfinite(g).all() for g in batch.values())
+    return {k: (rel_err(batch[k], acc[k] / B), elem_err(batch[k], acc[k] / B, rtol=1e-4, atol_rms=1e-5)) for k in batch}
+
+
+def assert_batch_equals_mean_of_samples(errs: Dict[str, Tuple[float, float]], n_grads: int = 66) -> None:
+    """The bar of `batch_vs_single_sample_grads`: every trainable gradient within 1e-5 in the max norm (the bar the suite
+    uses for the spatial stage's atomics) and element-wise |a-b| <= 1e-4*|b| + 1e-5*rms(b)."""
+    worst = max(errs.items(), key=lambda kv: kv[1][0])
+    worst_e = max(errs.items(), key=lambda kv: kv[1][1])
+    print(f"batch vs mean of samples: max-norm {worst[1][0]:.2e} ({worst[0]}), element-wise {worst_e[1][1]:.3f} of the "
+          f"bar ({worst_e[0]})")
+    assert len(errs) == n_grads, sorted(errs)
+    bad = {k: v for k, v in errs.items() if not (v[0] <= 1e-5 and v[1] < 1.0)}
+    assert not bad, bad
+
+
 def assert_parity(res: dict, tol: Optional[float] = None, kink: bool = False, elem_scale: Optional[dict] = None,
                   small40: bool = False, small24: bool = False) -> None:
     """The bar of every full-step test.  fp32: forward, loss and all gradients within 1e-3 in the max norm AND

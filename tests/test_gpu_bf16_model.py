@@ -15,8 +15,9 @@ import pytest
 import torch
 
 from oracle import ref_cpu as R
-from tests.parity import (ATOL_RMS_BF16, RTOL_BF16, assert_close, assert_parity, build_model, compare_forward_backward, device_rounding,
-                          l2_rel, oracle_step)
+from tests.parity import (ATOL_RMS_BF16, RTOL_BF16, assert_batch_equals_mean_of_samples, assert_close, assert_parity,
+                          batch_vs_single_sample_grads, build_model, compare_forward_backward, device_rounding, l2_rel,
+                          oracle_step, rel_err)
 
 pytestmark = pytest.mark.gpu
 BF16 = 1                      # tecmollm.ops.PREC_BF16
@@ -252,6 +253,54 @@ def test_bf16_outlier_channels_like_a_pretrained_gpt2(dev):
     # everything in front of it doubles); a store that dropped the small channels would show as O(1)
     for e, k in errs:
         assert e < (1e-1 if k in GAT_TENSORS else 6e-2), errs[:6]
+
+
+def test_bf16_full_size_batch_of_8_gradients_equal_mean_of_single_samples(dev):
+    """bf16 mode as `bench.py --precision bf16` times it, eval mode, B = 8: the 66 gradients of the batch step equal the mean
+    of the eight single-sample steps' gradients (tests/parity.py:batch_vs_single_sample_grads).  The forward is per-sample
+    bit-exact and the batch's loss gradient is the single-sample one times 1/8 (exact, and exact through every bf16
+    rounding), so the fp32 bar holds here too although the batch runs other tile heights and split-K counts."""
+    cfg = R.default_config(L_in=48, L_out=12, num_nodes=2911, c_in=10, d_emb=12)
+    assert_batch_equals_mean_of_samples(batch_vs_single_sample_grads(cfg, 8, (41, 71), seed=45, precision="bf16"))
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+
+
+def test_bf16_train_mode_p0_full_size_batch_of_8_equals_eval(dev, monkeypatch):
+    """Training mode at B = 8 in bf16 mode with p = 0 (every dropout site's plumbing engaged, nothing dropped) against eval
+    mode on the same batch: the forward bit for bit, the 55 gradients behind the spatial stage bit for bit, the 11 of the
+    spatial stage (float atomics) to 1e-5.  With the test above this ties the training-mode B = 8 step to the per-sample
+    oracle checks; an oracle run of the bf16 B = 8 step (about a minute of CPU and 30 GB of host memory) is not part of the
+    suite -- the fp32 one is (tests/test_gpu_model.py::test_train_mode_full_size_batch_of_8_against_oracle)."""
+    import dataclasses
+    import src.model.tec_mollm as TM
+    cfg = R.default_config(L_in=48, L_out=12, num_nodes=2911, c_in=10, d_emb=12)
+    model = build_model(cfg, R.init_params(cfg, seed=46), dev, "per_timestep", precision="bf16")
+    x, tf, y = R.synthetic_batch(8, 48, 2911, 10, 12, seed=146)
+    ei = R.grid_graph()[0].to(dev)
+    xd, yd = x.to(dev), y.to(dev)
+    tfd = tf[:, :, 0, :].contiguous().to(dev).unsqueeze(-2).expand(8, 48, 2911, 4)
+    orig = TM.make_plan
+    monkeypatch.setattr(TM, "make_plan", lambda m, p=0.1, precision="auto": dataclasses.replace(orig(m, p, precision), p=0.0))
+
+    def step(train):
+        model.train(train)
+        model.zero_grad(set_to_none=True)
+        out = model(xd, tfd, ei)
+        torch.nn.functional.huber_loss(out, yd).backward()
+        return out.detach().clone(), {k: v.grad.clone() for k, v in model.named_parameters() if v.grad is not None}
+    out_t, g_t = step(True)
+    out_e, g_e = step(False)
+    assert torch.isfinite(out_t).all() and torch.equal(out_t, out_e)
+    assert len(g_t) == 66 and g_t.keys() == g_e.keys() and all(torch.isfinite(v).all() for v in g_t.values())
+    spatial = [k for k in g_t if k.startswith(("spatio_temporal_embedding.", "spatial_encoder."))]
+    assert len(spatial) == 11
+    assert all(torch.equal(g_t[k], g_e[k]) for k in g_t if k not in spatial), \
+        [k for k in g_t if k not in spatial and not torch.equal(g_t[k], g_e[k])]
+    assert all(rel_err(g_t[k], g_e[k]) < 1e-5 for k in spatial), [(k, rel_err(g_t[k], g_e[k])) for k in spatial]
+    model.zero_grad(set_to_none=True)
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
 
 
 def test_bf16_train_mode_full_size_graph_F10(dev):

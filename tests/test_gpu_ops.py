@@ -516,6 +516,105 @@ def test_attention_dropout_mask_is_consistent(dev):
     assert _rel(dqkv, g) < TOL
 
 
+# The backward's instances by input type: fp32 qkv; bf16 qkv (Q16: bf16 mode's c_attn output); bf16 qkv and bf16 dctx (D16:
+# the gradient the bf16 attn.c_proj d-input GEMM returns).  The forward's two are fp32 / bf16 qkv.
+ATT_BWD = {"f32": (False, False), "q16": (True, False), "q16_d16": (True, True)}
+
+
+def _att_case(dev, Bn, T, N, q16, d16, p, grad=True, seed=777):
+    """Inputs in the form the instance reads them, the dropout spec, and the float64 reference (forward, d qkv) computed on
+    exactly the values the kernel reads, with the mask mirrored through rng.keep_mult (index layout of the kernel:
+    (((b*N + n)*H + h)*T + i)*T + j, as in test_attention_dropout_mask_is_consistent)."""
+    from tecmollm import ops, rng
+    H, D = 12, 768
+    qkv = _rand(Bn, T, N, 3 * D, dev=dev, seed=T, scale=0.5)
+    dctx = _rand(Bn, T, N, D, dev=dev, seed=100 + T)
+    q_in = qkv.bfloat16() if q16 else qkv
+    d_in = dctx.bfloat16() if d16 else dctx
+    keep, drop = None, None
+    if p:
+        idx = np.arange(Bn * N * H * T * T, dtype=np.uint64)
+        keep = torch.from_numpy(rng.keep_mult(seed, idx, p)).double().view(Bn, N, H, T, T).to(dev)
+        drop = ops.drop(p, seed, 1)
+    qd = q_in.double().requires_grad_(grad)
+    ref = _ref_attention(qd, Bn, T, N, H, D, keep)
+    gref = torch.autograd.grad(ref, qd, d_in.double())[0] if grad else None
+    return q_in, d_in, drop, ref.detach(), gref
+
+
+def _assert_att(a, b, what):
+    """Max-norm TOL and element-wise |a-b| <= TOL*|b| + 0.1*TOL*rms(b): a wrong entry that is small next to the largest one
+    (a wrong mask element, a dropped term of a short row) fails too."""
+    assert _rel(a, b) < TOL, (what, _rel(a, b))
+    a, b = a.double(), b.double()
+    rms = float(b.pow(2).mean().sqrt())
+    e = float(((a - b).abs() / (TOL * b.abs() + 0.1 * TOL * rms + 1e-300)).max())
+    assert e < 1.0, (what, e)
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1], ids=["nodrop", "drop"])
+@pytest.mark.parametrize("inst", list(ATT_BWD))
+@pytest.mark.parametrize("T", range(1, 33))
+def test_attention_every_t_matches_float64(dev, T, inst, p):
+    """Every T the launchers accept (1..32: the compile-time instances T = 1, 2, 3, 4, 6 (8, 12: the wide backward), the
+    register-resident k / v forward and the q-streaming backward for 12 < T <= 24, the runtime-T path elsewhere), every
+    input-type instance, dropout off and on: forward and backward against float64, into NaN-filled outputs; the bf16
+    outputs are the round-to-nearest-even of the fp32 ones."""
+    from tecmollm import ops
+    q16, d16 = ATT_BWD[inst]
+    Bn, N, H, D = 2, 7, 12, 768
+    q_in, d_in, drop, ref, gref = _att_case(dev, Bn, T, N, q16, d16, p)
+    nan = float("nan")
+    if not d16:                                     # the forward reads qkv only: once per forward instance
+        ctx = torch.full(ref.shape, nan, device=dev)
+        ops.attention_fwd(q_in, ctx, Bn, T, N, H, D, drop)
+        _assert_att(ctx, ref, "ctx")
+        ctx16 = torch.full(ref.shape, nan, device=dev, dtype=torch.bfloat16)
+        ops.attention_fwd(q_in, ctx16, Bn, T, N, H, D, drop)
+        assert torch.equal(ctx16, ctx.bfloat16())
+    dq = torch.full(q_in.shape, nan, device=dev)
+    ops.attention_bwd(q_in, d_in, dq, Bn, T, N, H, D, drop)
+    _assert_att(dq, gref, "dqkv")
+    dq16 = torch.full(q_in.shape, nan, device=dev, dtype=torch.bfloat16)
+    ops.attention_bwd(q_in, d_in, dq16, Bn, T, N, H, D, drop)
+    assert torch.equal(dq16, dq.bfloat16())
+
+
+# The q-streaming backward (csrc/attention.hip, 12 < T <= 24) sits at the edge of the register file, and its documented
+# failure mode was non-reproducible output.  A grid of 600 blocks (more than one wave of blocks on 256 CUs), three launches
+# into NaN-filled buffers: bit-identical, complete, and right.
+@pytest.mark.parametrize("p", [0.0, 0.1], ids=["nodrop", "drop"])
+@pytest.mark.parametrize("inst", list(ATT_BWD))
+@pytest.mark.parametrize("T", [13, 16, 20, 21, 24])
+def test_attention_bwd_qstream_reproducible(dev, T, inst, p):
+    from tecmollm import ops
+    q16, d16 = ATT_BWD[inst]
+    Bn, N, H, D = 2, 400, 12, 768                   # 9 600 (sequence, head) items, 16 per block
+    q_in, d_in, drop, _, gref = _att_case(dev, Bn, T, N, q16, d16, p)
+    outs = [torch.full(q_in.shape, float("nan"), device=dev) for _ in range(3)]
+    for o in outs:
+        ops.attention_bwd(q_in, d_in, o, Bn, T, N, H, D, drop)
+    assert not bool(torch.isnan(outs[0]).any())
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    _assert_att(outs[0], gref, "dqkv")
+
+
+@pytest.mark.parametrize("p", [0.0, 0.1], ids=["nodrop", "drop"])
+@pytest.mark.parametrize("q16", [False, True], ids=["f32", "q16"])
+@pytest.mark.parametrize("T", [13, 16, 20, 21, 24])
+def test_attention_fwd_kv_reproducible(dev, T, q16, p):
+    """The same screen for the register-resident k / v forward (12 < T <= 24)."""
+    from tecmollm import ops
+    Bn, N, H, D = 2, 400, 12, 768
+    q_in, _, drop, ref, _ = _att_case(dev, Bn, T, N, q16, False, p, grad=False)
+    outs = [torch.full(ref.shape, float("nan"), device=dev) for _ in range(3)]
+    for o in outs:
+        ops.attention_fwd(q_in, o, Bn, T, N, H, D, drop)
+    assert not bool(torch.isnan(outs[0]).any())
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    _assert_att(outs[0], ref, "ctx")
+
+
 @pytest.mark.parametrize("L,Cout", [(48, 64), (24, 128), (96, 64), (336, 64), (168, 128), (100, 64), (12, 256)])
 def test_gn_reg_ok_mirrors_the_library(dev, L, Cout):
     """ops.gn_reg_ok (what decides whether a conv block keeps bf16 activations) against the library itself: bf16 act / dy

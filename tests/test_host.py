@@ -641,6 +641,45 @@ _Zkernel:
         with pytest.raises(RuntimeError):
             ge.audit_hand_issued_lds_reads(bad, "bad")
 
+def _remarks(spills, scratch=None):
+    """A kernel-resource-usage remark block in hipcc's format: {mangled kernel name: VGPRs Spill}, ScratchSize given or
+    derived from the spill count."""
+    out = []
+    for name, n in spills.items():
+        out += [f"attention.hip:284:1: remark: Function Name: {name} [-Rpass-analysis=kernel-resource-usage]",
+                "  284 |                                                                        int N, int H, int D, DropA dr) {",
+                "      | ^"]
+        for field, v in (("TotalSGPRs", 84), ("VGPRs", 256), ("AGPRs", 256), ("ScratchSize [bytes/lane]", scratch if scratch is not None else 8 + 4 * n),
+                         ("Occupancy [waves/SIMD]", 1), ("SGPRs Spill", 0), ("VGPRs Spill", n), ("LDS Size [bytes/block]", 0)):
+            out.append(f"attention.hip:284:1: remark:     {field}: {v} [-Rpass-analysis=kernel-resource-usage]")
+    return "\n".join(out)
+
+
+def test_spill_ceiling_parser_of_the_build():
+    """__graft_entry__.check_spill_ceilings (run by build() on the remarks of every source in SPILL_CEILINGS): the attention
+    backward's qstream instances pass at their ceilings, and the build fails -- naming the kernel -- one VGPR above, or
+    when an instance's remark is missing."""
+    import __graft_entry__ as ge
+    rules = ge.SPILL_CEILINGS["attention.hip"]
+    f32 = "_ZN12_GLOBAL__N_128attention_bwd_kernel_qstreamILi24ELb0ELb0EEEvPKfS2_PfiiiiiiNS_5DropAE"
+    q16 = "_ZN12_GLOBAL__N_128attention_bwd_kernel_qstreamILi24ELb1ELb0EEEvPKfS2_PfiiiiiiNS_5DropAE"
+    d16 = "_ZN12_GLOBAL__N_128attention_bwd_kernel_qstreamILi24ELb1ELb1EEEvPKfS2_PfiiiiiiNS_5DropAE"
+    other = "_ZN12_GLOBAL__N_120attention_bwd_kernelILi0ELb0ELb0EEEvPKfS2_PfiiiiiiNS_5DropAE"      # not ceilinged
+    today = {other: 400, d16: 18, q16: 18, f32: 92}
+    ge.check_spill_ceilings("attention.hip", _remarks(today), rules)
+    ge.check_spill_ceilings("attention.hip", _remarks(dict(today, **{f32: 0, q16: 3})), rules)
+    for name in (f32, q16, d16):
+        with pytest.raises(RuntimeError, match=name):
+            ge.check_spill_ceilings("attention.hip", _remarks(dict(today, **{name: today[name] + 1})), rules)
+        with pytest.raises(RuntimeError, match="no remark for .*qstream"):
+            ge.check_spill_ceilings("attention.hip", _remarks({k: v for k, v in today.items() if k != name}), rules)
+    # the zero-scratch rule of the hand-issued-load kernel goes through the same parser
+    dw = {"_Z18conv_dw_seq_kernelILi4EEvPKf": 0}
+    ge.check_spill_ceilings("conv_dw_seq.hip", _remarks(dw, scratch=0), ge.SPILL_CEILINGS["conv_dw_seq.hip"])
+    with pytest.raises(RuntimeError, match="conv_dw_seq_kernel"):
+        ge.check_spill_ceilings("conv_dw_seq.hip", _remarks(dw, scratch=16), ge.SPILL_CEILINGS["conv_dw_seq.hip"])
+
+
 def test_bench_line_stays_under_the_drivers_parse_budget():
     """The driver parses the LAST stdout line of bench.py out of ~8 KB of kept tail.  Round 4's line (committed as
     profiles/r04_bench_default.json: 24 KB with per-shape tables) was cut -> parsed: null.  compact_line() must turn that

@@ -299,7 +299,9 @@ int tecm_layernorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t ld
 
 /* Causal multi-head self-attention over T tokens per sequence (GPT2Attention, modeling_gpt2.py:54-73,
  * :144-226; all-ones attention_mask tec_mollm.py:111 => pure causal).  qkv: (B,T,N,3*D) time-major
- * rows, ctx: (B,T,N,D).  head_dim = D/heads must be 64.  Dropout on the probabilities. */
+ * rows, ctx: (B,T,N,D).  head_dim = D/heads must be 64.  1 <= T <= 1024 (GPT-2's positions; T > 32 runs the matrix-core
+ * kernels of attention_long.hip, same layout and results contract).  Dropout on the probabilities, 64-bit index
+ * (((b*N + n)*heads + h)*T + i)*T + j. */
 /* io_bf16: TECM_ATT_OUT_BF16 -- ctx is a bf16 (B,T,N,D) tensor (its only reader, attn.c_proj, is a bf16 GEMM);
  * TECM_ATT_QKV_BF16 -- qkv is a bf16 (B,T,N,3*D) tensor (bf16 mode: the c_attn GEMM stores its output as bf16, which is
  * what a Linear's output is under torch.autocast, train.py:68; scores, softmax and the weighted sum stay fp32). */

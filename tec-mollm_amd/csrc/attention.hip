@@ -1,5 +1,7 @@
-// Causal multi-head attention over the T (<= 32) latent-patch tokens of one (b, n) sequence --
+// Causal multi-head attention over the T latent-patch tokens of one (b, n) sequence --
 // GPT2Attention with an all-ones mask (modeling_gpt2.py:54-73, :144-226; tec_mollm.py:111).
+// The entry points accept 1 <= T <= 1024 (GPT-2's positions); this file holds the kernels for T <= 32 and sends
+// 33 <= T <= 1024 to the matrix-core kernels of attention_long.hip (same layout, dropout index and outputs).
 //
 // T is tiny (3 for L_in=48, 6 for 96, 21 for 336) while there are B*N*12 independent (sequence, head)
 // problems, so this is a bandwidth kernel, not an MFMA one: 16 lanes own one (sequence, head), each
@@ -8,6 +10,7 @@
 // Rows are time-major: token p of sequence (b, n) is row (b*T + p)*N + n of the (B,T,N,3D) qkv buffer.
 // Dropout on the probabilities uses idx = (((b*N + n)*H + h)*T + i)*T + j.
 #include "common.h"
+#include "attention_long.h"
 
 namespace {
 
@@ -378,7 +381,7 @@ __global__ __launch_bounds__(256, 1) void attention_bwd_kernel_wide(const float*
 
 int check(const char* who, const void* a, const void* b, const void* c, int B, int T, int N, int heads, int D) {
   TECM_REQUIRE(a && b && c, TECM_E_ARG, "%s: null pointer", who);
-  TECM_REQUIRE(B > 0 && N > 0 && T > 0 && T <= 32, TECM_E_ARG, "%s: need 1 <= T <= 32 (got %d)", who, T);
+  TECM_REQUIRE(B > 0 && N > 0 && T > 0 && T <= 1024, TECM_E_ARG, "%s: need 1 <= T <= 1024 (got %d)", who, T);
   TECM_REQUIRE(heads > 0 && D == heads * 64, TECM_E_ARG, "%s: head_dim must be 64 (D=%d heads=%d)", who, D, heads);
   TECM_REQUIRE(tecm_aligned(a, 16) && tecm_aligned(b, 16) && tecm_aligned(c, 16), TECM_E_ALIGN,
                "%s: 16-byte alignment required", who);
@@ -402,6 +405,7 @@ extern "C" int tecm_attention_fwd(const float* qkv, void* ctxv, int32_t io_bf16,
   const int rc = check("tecm_attention_fwd", qkv, ctx, ctx, B, T, N, heads, D);
   if (rc) return rc;
   TECM_REQUIRE((io_bf16 & ~3) == 0, TECM_E_ARG, "tecm_attention_fwd: io_bf16 is a mask of TECM_ATT_OUT_BF16 | TECM_ATT_QKV_BF16");
+  if (T > 32) return att_long_fwd(qkv, ctx, io_bf16, B, T, N, heads, prob_drop, (hipStream_t)stream);
   const int ctx_bf16 = io_bf16 & TECM_ATT_OUT_BF16;
   const bool q16 = (io_bf16 & TECM_ATT_QKV_BF16) != 0;
   const int64_t items = (int64_t)B * N * heads;
@@ -443,6 +447,7 @@ extern "C" int tecm_attention_bwd(const float* qkv, const float* dctx, void* dqk
   TECM_REQUIRE((io_bf16 & ~7) == 0 && (!(io_bf16 & TECM_ATT_DCTX_BF16) || (io_bf16 & TECM_ATT_QKV_BF16)), TECM_E_ARG,
                "tecm_attention_bwd: io_bf16 is a mask of TECM_ATT_OUT_BF16 | TECM_ATT_QKV_BF16 | TECM_ATT_DCTX_BF16 (the last "
                "only with a bf16 qkv)");
+  if (T > 32) return att_long_bwd(qkv, dctx, dqkv, io_bf16, B, T, N, heads, prob_drop, (hipStream_t)stream);
   const int dqkv_bf16 = io_bf16 & TECM_ATT_OUT_BF16;
   const bool q16 = (io_bf16 & TECM_ATT_QKV_BF16) != 0, d16 = (io_bf16 & TECM_ATT_DCTX_BF16) != 0;
   const int64_t items = (int64_t)B * N * heads;

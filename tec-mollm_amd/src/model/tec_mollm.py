@@ -85,6 +85,9 @@ class TEC_MoLLM(nn.Module):
         if conv_len % cfg["patch_len"] != 0:
             raise ValueError("patch_len must divide temporal_seq_len // (s0*s1) (train.py:255-260)")
         self.num_patches = conv_len // cfg["patch_len"]
+        if self.num_patches > 1024:
+            raise ValueError(f"num_patches = {self.num_patches} > 1024: GPT-2 has 1024 positions (wpe rows); "
+                             "shorten temporal_seq_len or raise patch_len")
         self.prediction_head = PredictionHead(input_dim=cfg["d_llm"] * self.num_patches,
                                               output_dim=cfg["prediction_horizon"])
         self.c_spatial = c_spatial

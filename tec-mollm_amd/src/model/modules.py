@@ -12,6 +12,7 @@ There is no PyTorch fallback: tensors must be CUDA (ROCm) fp32, otherwise the ca
 """
 from __future__ import annotations
 
+import dataclasses
 import logging
 import math
 from typing import List, Optional
@@ -22,6 +23,7 @@ import torch.nn as nn
 import os
 
 from tecmollm import functions as F_
+from tecmollm import memory as mem_
 from tecmollm import ops as ops_
 from tecmollm import graph as graph_
 from tecmollm._lib import TecmError
@@ -36,16 +38,22 @@ def autocast_bf16() -> bool:
     return torch.is_autocast_enabled("cuda") and torch.get_autocast_dtype("cuda") == torch.bfloat16
 
 
-def make_plan(module: nn.Module, p: float = 0.1, precision: str = "auto") -> F_.DropPlan:
-    """One plan per forward call: dropout seeds (base seed = torch seed + call count) and the GEMM precision:
-    "fp32" = exact-f32 MFMA, "bf16" = bf16 MFMA with fp32 accumulate, "auto" = bf16 iff under bf16 autocast,
-    "bf16x3" = fp32 emulated by three bf16 MFMAs per product on the plain GPT-2 GEMMs (opt-in, ~1e-5)."""
-    _seed_counter[0] += 1
+def precision_code(precision: str = "auto"):
+    """The GEMM precision of a forward called here and now (see make_plan): False / True (bf16), 2 (bf16x3), 3 (bf16x6)."""
     bf16 = precision == "bf16" or (precision == "auto" and autocast_bf16())
     if precision == "bf16x3":
         bf16 = 2                                   # ops.PREC_BF16X3
     elif precision == "bf16x6":
         bf16 = 3                                   # ops.PREC_BF16X6
+    return bf16
+
+
+def make_plan(module: nn.Module, p: float = 0.1, precision: str = "auto") -> F_.DropPlan:
+    """One plan per forward call: dropout seeds (base seed = torch seed + call count) and the GEMM precision:
+    "fp32" = exact-f32 MFMA, "bf16" = bf16 MFMA with fp32 accumulate, "auto" = bf16 iff under bf16 autocast,
+    "bf16x3" = fp32 emulated by three bf16 MFMAs per product on the plain GPT-2 GEMMs (opt-in, ~1e-5)."""
+    _seed_counter[0] += 1
+    bf16 = precision_code(precision)
     return F_.DropPlan(training=module.training, p=p, base_seed=(torch.initial_seed() + 7919 * _seed_counter[0]),
                        bf16=bf16)
 
@@ -73,9 +81,10 @@ class Multi_Scale_Conv_Block(nn.Module):
         self.final_conv = nn.Conv1d(out_channels * len(kernel_sizes), out_channels, kernel_size=1, stride=stride)
 
     def forward_tm(self, inp: torch.Tensor, cin: int, need_dinp: bool = True, bf16: bool = False,
-                   inp16: Optional[torch.Tensor] = None):
+                   inp16: Optional[torch.Tensor] = None, recompute: bool = False):
         """inp (B, Lc, N, ld) time-major with `cin` real channels -> (out (B, Lc/stride, N, Cout), out16): out16 is a
-        bf16 copy of out in bf16 mode (None otherwise) for the window GEMMs of the next stage; inp16 likewise."""
+        bf16 copy of out in bf16 mode (None otherwise) for the window GEMMs of the next stage; inp16 likewise.
+        recompute: keep only the input for the backward, which rebuilds the rest (recompute level 2)."""
         args = []
         for seq in self.convs:
             args += [seq[0].weight, seq[0].bias, seq[1].weight, seq[1].bias]
@@ -84,8 +93,8 @@ class Multi_Scale_Conv_Block(nn.Module):
             # so that the sequence-tile kernels -- and with them the bf16 storage of y -- serve this call as they serve the model
             inp16 = torch.empty(inp.shape, device=inp.device, dtype=torch.bfloat16)
             ops_.cast_bf16(inp.detach(), inp.shape[-1], inp16, inp.shape[-1], inp.numel() // inp.shape[-1], inp.shape[-1])
-        return F_.ConvBlockFn.apply(inp, inp16, cin, self.stride, need_dinp, bf16, *args, self.final_conv.weight,
-                                    self.final_conv.bias)
+        return F_.ConvBlockFn.apply(inp, inp16, cin, self.stride, need_dinp, bf16, bool(recompute), *args,
+                                    self.final_conv.weight, self.final_conv.bias)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """Reference signature: x (S, C_in, L) -> (S, C_out, L_out)."""
@@ -109,7 +118,7 @@ class MultiScaleConvEmbedder(nn.Module):
             cur = out_channels
         self.embedder = nn.Sequential(*layers)
 
-    def forward_tm(self, inp: torch.Tensor, cin: int, need_dinp: bool = True, bf16: bool = False):
+    def forward_tm(self, inp: torch.Tensor, cin: int, need_dinp: bool = True, bf16: bool = False, recompute: bool = False):
         inp16 = None
         if int(bf16) == ops_.PREC_BF16 and inp.shape[-1] % 8 == 0 and os.environ.get("TECM_XS16", "1")[:1] != "0":
             # bf16 mode: the first block's window GEMMs (three forward convs, three weight gradients: 15 tap reads of
@@ -118,7 +127,7 @@ class MultiScaleConvEmbedder(nn.Module):
             rows = inp.numel() // inp.shape[-1]
             ops_.cast_bf16(inp.detach(), inp.shape[-1], inp16, inp.shape[-1], rows, inp.shape[-1])
         for i, blk in enumerate(self.embedder):
-            inp, inp16 = blk.forward_tm(inp, cin, need_dinp or i > 0, bf16, inp16)
+            inp, inp16 = blk.forward_tm(inp, cin, need_dinp or i > 0, bf16, inp16, recompute)
             cin = blk.out_channels
         return inp, inp16
 
@@ -158,7 +167,8 @@ class TemporalEncoder(nn.Module):
         self.patcher = LatentPatchingProjection(channel_list[-1], patch_len, d_llm)
 
     def forward_tm(self, inp, cin, wpe, plan, need_dinp=True):
-        conv, conv16 = self.conv_embedder.forward_tm(inp, cin, need_dinp, plan.bf16)
+        conv, conv16 = self.conv_embedder.forward_tm(inp, cin, need_dinp, plan.bf16,
+                                                     recompute=plan.keep and plan.recompute >= 2)
         return self.patcher.forward_tm(conv, wpe, plan, conv16)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -253,7 +263,8 @@ class _PeftGPT2(nn.Module):
         self.base_model = _BaseModel(trunk)
 
     def gradient_checkpointing_enable(self, *args, **kwargs):
-        # Nothing to recompute: activations are kept (288 GB HBM); the reference re-enables this every step.
+        """Harmless (the reference calls it every step, train.py:70-73): recomputation engages on its own when a step would
+        not fit the device -- TEC_MoLLM.forward picks the level (tecmollm/memory.py); a step that fits keeps everything."""
         return None
 
     def print_trainable_parameters(self):
@@ -311,6 +322,7 @@ class LLMBackbone(nn.Module):
             with torch.no_grad():
                 _load_pretrained_gpt2(trunk)
         self.num_layers = num_layers_to_keep
+        self.recompute_level = 0                         # the level the last forward ran at (tecmollm/memory.py)
         self.model = _PeftGPT2(trunk)
         self._freeze_parameters()
 
@@ -346,6 +358,14 @@ class LLMBackbone(nn.Module):
         _need_cuda(inputs_embeds, "inputs_embeds")
         S, T, D = inputs_embeds.shape
         plan = make_plan(self)
+        # no backward will run: the lean forward; otherwise the smallest recompute level that fits (0 or 1 for the stack)
+        keep = torch.is_grad_enabled() and (inputs_embeds.requires_grad or any(p.requires_grad for p in self.parameters()))
+        prec = int(plan.bf16)
+        key = ("stack", S, T, self.num_layers, prec, plan.training, keep)
+        level = mem_.choose(key, lambda lv: mem_.estimate_stack(S, T, 1, self.num_layers, prec, lv, plan.training, keep),
+                            inputs_embeds.device, levels=(0, 1), what="LLMBackbone.forward") if keep else 0
+        self.recompute_level = level
+        plan = dataclasses.replace(plan, recompute=level, keep=keep)
         wpe = self.trunk.wpe.weight
         h0 = inputs_embeds + wpe[:T]                     # stand-alone use only; fused path adds wpe in the GEMM
         if plan.training and plan.p > 0:

@@ -29,8 +29,9 @@ import torch.nn as nn
 
 from tecmollm import functions as F_
 from tecmollm import graph as graph_
+from tecmollm import memory as mem_
 from .modules import (LLMBackbone, PredictionHead, SpatialEncoder, SpatioTemporalEmbedding, TemporalEncoder,
-                      _need_cuda, make_plan)
+                      _need_cuda, make_plan, precision_code)
 
 log = logging.getLogger(__name__)
 
@@ -92,6 +93,26 @@ class TEC_MoLLM(nn.Module):
                                               output_dim=cfg["prediction_horizon"])
         self.c_spatial = c_spatial
         self.heads = cfg["spatial_heads"]
+        self.model_config = dict(cfg)
+        self._cfg_key = tuple(sorted((k, str(v)) for k, v in cfg.items()))
+        self.recompute_level = 0          # the recompute level the last forward ran at (tecmollm/memory.py)
+
+    def precision_code(self) -> int:
+        """The precision code (ops.PREC_*) a forward called here and now runs at (make_plan)."""
+        return int(precision_code(self.precision))
+
+    def recompute_level_for(self, B: int, precision: int, grad: bool = True) -> int:
+        """The recompute level a forward of batch B runs at in this precision code (ops.PREC_*), training mode and grad
+        mode: the smallest level whose estimated step fits the device (tecmollm/memory.py), cached per configuration so
+        that it does not flip from step to step; TECM_RECOMPUTE forces a level or a budget.  No backward (grad False): 0,
+        and the forward is the lean one."""
+        if not grad:
+            return 0
+        cfg = self.model_config
+        key = ("model", self._cfg_key, B, int(precision), self.training, grad)
+        fuse = _fuse_head()
+        return mem_.choose(key, lambda lv: mem_.estimate(cfg, B, int(precision), lv, self.training, grad, fuse_head=fuse),
+                           self.prediction_head.mlp[0].weight.device, what="TEC_MoLLM.forward")
 
     def forward(self, x: torch.Tensor, time_features: torch.Tensor, edge_index: torch.Tensor,
                 edge_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -105,6 +126,11 @@ class TEC_MoLLM(nn.Module):
         if time_features.shape != (B, L, N, 4):
             raise ValueError(f"time_features must be (B, L, N, 4), got {tuple(time_features.shape)}")
         plan = make_plan(self, precision=self.precision)
+        # recomputation (tecmollm/memory.py): level 0 -- everything kept -- wherever the step fits; no backward will run
+        # (grad mode off, or nothing requires grad): the lean forward, which keeps nothing across GPT-2 blocks
+        keep = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        self.recompute_level = self.recompute_level_for(B, int(plan.bf16), keep)
+        plan = dataclasses.replace(plan, recompute=self.recompute_level, keep=keep)
         meta = graph_.get(edge_index, N, x.device, self.spatio_temporal_embedding.d_emb)
         R = 1 if self.gat_graphs == "reference" else B * L
         # 1-4. embedding + GATv2 + residual  -> (B, L, N, 24) time-major

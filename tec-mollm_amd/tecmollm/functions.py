@@ -61,6 +61,10 @@ class DropPlan:
     base_seed: int
     bf16: bool = False      # run the dense contractions on the bf16 matrix cores (autocast semantics)
     fuse_head: bool = False  # bf16 mode, whole model: ln_f writes the head's operand directly (see GPT2StackFn / HeadFn)
+    # activation recomputation (tecmollm/memory.py picks it): 0 = every stage keeps what its backward reads; 1 = the GPT-2
+    # blocks keep their input h only and re-run their forward in the backward; 2 = 1 + the conv blocks keep their input only
+    recompute: int = 0
+    keep: bool = True        # False: no backward will run (grad mode off, or nothing requires grad): keep nothing across layers
 
     def spec(self, site: int, ld: int):
         if not self.training or self.p <= 0.0:
@@ -323,10 +327,11 @@ class ConvBlockFn(torch.autograd.Function):
     (ld_in - cin zero pad channels); returns (B, Lc//stride, N, Cout)."""
 
     @staticmethod
-    def forward(ctx, inp, inp16, cin: int, stride: int, need_dinp: bool, bf16: bool,
+    def forward(ctx, inp, inp16, cin: int, stride: int, need_dinp: bool, bf16: bool, recompute: bool,
                 w3, b3, g3, be3, w5, b5, g5, be5, w7, b7, g7, be7, wf, bf):
         """inp16: optional bf16 copy of inp (bf16 mode: written by the producing block's last GEMM next to its fp32 output;
-        only the forward window GEMMs read it).  Returns (out, out16): out16 is that copy of this block's output, or None."""
+        only the forward window GEMMs read it).  Returns (out, out16): out16 is that copy of this block's output, or None.
+        recompute (level 2): keep only what the block received; the backward rebuilds y, the statistics and act."""
         B, Lc, N, ld_in = inp.shape
         Cout = w3.shape[0]
         CT = 3 * Cout
@@ -358,11 +363,12 @@ class ConvBlockFn(torch.autograd.Function):
         stats = _empty(B * N, 3, 2, like=inp)
         st_given = y16 and ops.conv_fwd_stats_ok(Lc)
         if fwd_seq:
-            ops.conv_fwd(seq_in.detach(), w3.detach(), w5.detach(), w7.detach(), bias3, y, B, Lc, N, Cout, cin, ld_in,
-                         stats=stats if st_given else None)
+            ConvBlockFn._conv_seq(seq_in, (w3, w5, w7), bias3, y, stats if st_given else None, B, Lc, N, Cout, cin, ld_in)
         # the window-GEMM operands ([Cout][k*ld_in] forward, [k*Cout][ld_in] d-input) are only packed when a GEMM will read
         # them: the forward below, or a backward whose sequence-tile kernels do not serve this shape / precision
         dx_gemm = need_dinp and not ConvBlockFn._dx_seq(bf16, r16, Lc, Cout, ld_in)
+        fps = []
+        a_in = inp16 if (inp16 is not None and side16 and ld_in % 8 == 0) else inp
         for j, (w, b) in enumerate(zip(ws, bs)):
             k = w.shape[2]
             if fwd_seq and not dx_gemm:
@@ -373,9 +379,8 @@ class ConvBlockFn(torch.autograd.Function):
             packs.append(bp)
             if fwd_seq:
                 continue
-            a_in = inp16 if (inp16 is not None and side16 and ld_in % 8 == 0) else inp
-            gemm(M, Cout, k * ld_in, a_in, ld_in, fp, k * ld_in, y, CT, c_off=j * Cout,
-                 a_win=win(N, Lc, Lc, 1, k, ld_in, (k - 1) // 2), bias=b, bf16=bf16)
+            fps.append(fp)
+            ConvBlockFn._conv_win(j, a_in, fp, b, y, M, B, Lc, N, Cout, ld_in, bf16)
         Lo = (Lc - 1) // stride + 1
         # the activation is only kept at the time steps the stride-s 1x1 conv reads (a COMPACT (B, Lo, N, CT) tensor: half
         # the bytes at stride 2, and that conv and its weight gradient become plain GEMMs, no window view) wherever the
@@ -383,8 +388,7 @@ class ConvBlockFn(torch.autograd.Function):
         compact = stride > 1 and ops.gn_reg_ok(Lc, N, Cout) and int(bf16) in (ops.PREC_FP32, ops.PREC_BF16)
         La = Lo if compact else Lc
         act = torch.empty(B, La, N, CT, device=inp.device, dtype=adt)
-        ops.groupnorm_gelu_fwd(y, gamma, beta, act, stats, B, Lc, N, Cout, act_stride=stride if compact else 1,
-                               stats_given=st_given)
+        ConvBlockFn._norm(y, gamma, beta, act, stats, B, Lc, N, Cout, stride if compact else 1, st_given)
         out = _empty(B, Lo, N, Cout, like=inp)
         wf2 = wf.view(Cout, CT)
         out16 = None
@@ -404,12 +408,53 @@ class ConvBlockFn(torch.autograd.Function):
             ctx.mark_non_differentiable(out16)
         else:
             gemm(B * Lo * N, Cout, CT, act, CT, wf2, CT, out, Cout, a_win=awin, bias=bf, bf16=bf16)
-        ctx.save_for_backward(inp, y, act, stats, gamma, beta, wf, *packs)
+        ctx.recompute = bool(recompute)
+        if recompute:
+            # what the block received and the recipe of y and act: the same launches with the same arguments in the backward
+            ctx.save_for_backward(inp, gamma, beta, wf, *packs)
+            ctx.rebuild = (seq_in if fwd_seq else None, a_in, fps, tuple(b.detach() for b in bs), bias3, y.dtype,
+                           act.shape, adt, st_given)
+            del y, act, stats
+        else:
+            ctx.save_for_backward(inp, y, act, stats, gamma, beta, wf, *packs)
         ctx.w357 = (w3.detach(), w5.detach(), w7.detach())       # raw (Cout, cin, k) weights: the fused d-inp kernel packs them
         ctx.inp16 = inp16 if (side16 and inp16 is not None and ld_in % 8 == 0) else None   # dW reads it instead of inp
         ctx.dims = (B, Lc, N, ld_in, cin, Cout, stride, Lo, need_dinp, bf16)
         ctx.compact = compact
         return out, out16
+
+    @staticmethod
+    def _conv_seq(seq_in, w357, bias3, y, stats, B, Lc, N, Cout, cin, ld_in):
+        """The three kernel sizes in one sequence-tile launch (forward, and the level-2 recompute)."""
+        ops.conv_fwd(seq_in.detach(), w357[0].detach(), w357[1].detach(), w357[2].detach(), bias3, y, B, Lc, N, Cout, cin,
+                     ld_in, stats=stats)
+
+    @staticmethod
+    def _conv_win(j, a_in, fp, b, y, M, B, Lc, N, Cout, ld_in, bf16):
+        """Kernel size 3 + 2j as a window GEMM into y's columns j*Cout.. (forward, and the level-2 recompute)."""
+        k = 3 + 2 * j
+        gemm(M, Cout, k * ld_in, a_in, ld_in, fp, k * ld_in, y, 3 * Cout, c_off=j * Cout,
+             a_win=win(N, Lc, Lc, 1, k, ld_in, (k - 1) // 2), bias=b, bf16=bf16)
+
+    @staticmethod
+    def _norm(y, gamma, beta, act, stats, B, Lc, N, Cout, act_stride, st_given):
+        ops.groupnorm_gelu_fwd(y, gamma, beta, act, stats, B, Lc, N, Cout, act_stride=act_stride, stats_given=st_given)
+
+    @staticmethod
+    def _rebuild(ctx, gamma, beta):
+        """Level 2: y, the GroupNorm statistics and act again, by the forward's launches with the forward's arguments."""
+        B, Lc, N, ld_in, cin, Cout, stride, Lo, need_dinp, bf16 = ctx.dims
+        seq_in, a_in, fps, bs, bias3, ydt, ashape, adt, st_given = ctx.rebuild
+        y = torch.empty(B, Lc, N, 3 * Cout, device=gamma.device, dtype=ydt)
+        stats = _empty(B * N, 3, 2, like=gamma)
+        if seq_in is not None:
+            ConvBlockFn._conv_seq(seq_in, ctx.w357, bias3, y, stats if st_given else None, B, Lc, N, Cout, cin, ld_in)
+        else:
+            for j, (fp, b) in enumerate(zip(fps, bs)):
+                ConvBlockFn._conv_win(j, a_in, fp, b, y, B * Lc * N, B, Lc, N, Cout, ld_in, bf16)
+        act = torch.empty(ashape, device=gamma.device, dtype=adt)
+        ConvBlockFn._norm(y, gamma, beta, act, stats, B, Lc, N, Cout, stride if ctx.compact else 1, st_given)
+        return y, act, stats
 
     @staticmethod
     def _dx_seq(bf16, dy16: bool, Lc: int, Cout: int, ld_in: int) -> bool:
@@ -419,7 +464,11 @@ class ConvBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _dout16=None):
-        inp, y, act, stats, gamma, beta, wf, bp3, bp5, bp7 = ctx.saved_tensors
+        if ctx.recompute:
+            inp, gamma, beta, wf, bp3, bp5, bp7 = ctx.saved_tensors
+            y, act, stats = ConvBlockFn._rebuild(ctx, gamma, beta)
+        else:
+            inp, y, act, stats, gamma, beta, wf, bp3, bp5, bp7 = ctx.saved_tensors
         B, Lc, N, ld_in, cin, Cout, stride, Lo, need_dinp, bf16 = ctx.dims
         CT = 3 * Cout
         M = B * Lc * N
@@ -485,7 +534,7 @@ class ConvBlockFn(torch.autograd.Function):
                 gemm(M, ld_in, k * Cout, dy, CT, bp, ld_in, dinp, ld_in, b_layout=B_KN, a_off=j * Cout,
                      a_win=win(N, Lc, Lc, 1, k, Cout, (k - 1) // 2), accumulate=(j > 0), bf16=bf16)
             grads += [dw, db, dgamma[j * Cout:(j + 1) * Cout], dbeta[j * Cout:(j + 1) * Cout]]
-        return (dinp, None, None, None, None, None, *grads, dwf.view_as(wf), dbf)
+        return (dinp, None, None, None, None, None, None, *grads, dwf.view_as(wf), dbf)
 
 
 # ============================================================================ stage a-5 (+ wpe / embd dropout of a-6)
@@ -663,89 +712,26 @@ class GPT2StackFn(torch.autograd.Function):
                                      "modules.py:195-203); freeze the GPT-2 base weights")
         B, T, N, D = h0.shape
         M = B * T * N
-        KE = D + LORA_R
         h = h0.contiguous()
+        level = plan.recompute if plan.keep else 0
         saved: List[torch.Tensor] = []
         ctx_lAT: List[Optional[torch.Tensor]] = []           # per layer: bf16 lora_A^T (bf16 mode) for the backward's dz . A, or None
         ctx_gen: List[int] = []                              # per layer: generation of the shared K-extended operand (see wcat)
+        ctx_wk: list = []                                    # recompute: per layer, the folded operands _block_fwd re-reads
         for i in range(n_layers):
-            (ln1w, ln1b, Wqkv, bqkv, lA, lB, Wo, bo, ln2w, ln2b, Wfc, bfc, Wpr,
-             bpr) = params[i * GPT2StackFn.PER_LAYER:(i + 1) * GPT2StackFn.PER_LAYER]
-            F3, F4 = Wqkv.shape[1], Wfc.shape[1]
-            b16 = int(plan.bf16) == ops.PREC_BF16           # bf16 mode: weights and GEMM-only activations live in HBM as bf16
-            wcatT = _frozen_copy(Wqkv, "kext_nk16" if b16 else "kext_nk32")   # [ W^T | (alpha/r) B ]: forward operand
-            Wo_f, ldo_f, lay_o = _fwd_weight(Wo, D, D, plan.bf16)
-            Wfc_f, ldfc_f, lay_fc = _fwd_weight(Wfc, D, F4, plan.bf16)
-            Wpr_f, ldpr_f, lay_pr = _fwd_weight(Wpr, F4, D, plan.bf16)
-            # Activations whose ONLY reader is a bf16 GEMM are written as bf16 by their producer (rounded once there
-            # instead of in that GEMM's loader: bit-identical, half the bytes both ways): LN1's output for c_attn, the
-            # attention context for attn.c_proj, LN2's output for c_fc, gelu(c_fc) for mlp.c_proj.
-            a16 = b16 and all(w is not None and w.dtype == torch.bfloat16 for w in (wcatT, Wo_f, Wfc_f, Wpr_f))
-            st1 = _empty(M, 2, like=h)
-            lspec = plan.spec(site_lora(i), KE)
-            if a16:
-                # bf16 mode: [ LN1(h) | z ] only ever feeds bf16 contractions, so it exists as bf16 alone (u16); the LoRA
-                # branch's input drop(LN1(h)) -- what autocast casts in front of lora_A -- is a second bf16 output of the
-                # LayerNorm kernel (u16d), read by the LoRA-A GEMM here and by its weight gradient in the backward, and z
-                # is written straight into u16's last 32 columns as bf16
-                u = None
-                u16 = torch.empty(M, KE, device=h.device, dtype=torch.bfloat16)
-                u16d = torch.empty(M, D, device=h.device, dtype=torch.bfloat16) if lspec is not None else None
-                ops.layernorm_fwd(h, D, ln1w, ln1b, None, KE, st1, M, D, y16=u16, ldy16=KE, y16d=u16d, ldy16d=D, drop16d=lspec)
-                a_lora, ld_lora = (u16d, D) if u16d is not None else (u16, KE)
-                # lora_A rounded (and transposed for its d-input contraction in the backward): both operands bf16 tensors
-                lA16, lAT16 = ops.weight_bf16(lA, same=True, transposed=True)
-                ctx_lAT.append(lAT16)
-                gemm(M, LORA_R, D, a_lora, ld_lora, lA16, D, u16, KE, c_off=D, bf16=plan.bf16)
-                u_s, ud_s = u16, (u16d if u16d is not None else h.new_empty(0))
-            else:
-                u = _empty(M, KE, like=h)                   # [ LN1(h) | z = drop(LN1(h)) A^T ]  (fp32: the LoRA gradients read it)
-                u16 = None
-                ops.layernorm_fwd(h, D, ln1w, ln1b, u, KE, st1, M, D)
-                gemm(M, LORA_R, D, u, KE, lA, D, u, KE, c_off=D, a_drop=lspec, bf16=plan.bf16)
-                u_s, ud_s = u, h.new_empty(0)
-                ctx_lAT.append(None)
-            # [ W ; (alpha/r) B^T ]  K-extended c_attn, backward operand ([KE][F3]) and forward operand ([F3][KE]): the
-            # frozen 768 x 2304 part of both is cached per parameter version (_frozen_copy), ONE launch refreshes the 32
-            # LoRA rows / columns of both from lora_B.  (The buffers are the cache's: they are rewritten by the next
-            # forward of this layer, normally after the backward that reads `wcat` has run.  The rewrite goes through a raw
-            # pointer, behind torch's version counter, so every fold bumps a generation number of the buffer and the backward
-            # checks it: a second forward of the same frozen base weight with an outstanding backward -- two adapters over
-            # one base, retain_graph across an optimizer step -- raises instead of differentiating against the wrong B.)
-            wcat = _frozen_copy(Wqkv, "kext_kn16" if b16 else "kext_kn32")
-            ops.lora_fold(lB.detach(), LORA_SCALE, wcat, wcatT, D)
-            _KEXT_GEN[wcat.data_ptr()] = _KEXT_GEN.get(wcat.data_ptr(), 0) + 1
-            ctx_gen.append(_KEXT_GEN[wcat.data_ptr()])
-            # bf16 mode: qkv is written as bf16 by the c_attn GEMM (what a Linear's output is under autocast) and read as
-            # such by the attention kernels, forward and backward: 644 -> 322 MB per layer, three times over
-            qkv = torch.empty(M, F3, device=h.device, dtype=torch.bfloat16 if (a16 and QKV16) else torch.float32)
-            gemm(M, F3, KE, u16 if a16 else u, KE, wcatT, KE, qkv, F3, b_layout=B_NK, bias=bqkv, bf16=plan.bf16)
-            cx = torch.empty(M, D, device=h.device, dtype=torch.bfloat16 if a16 else torch.float32)
-            aspec = plan.spec(site_attn(i), 1)
-            ops.attention_fwd(qkv, cx, B, T, N, GPT_HEADS, D, aspec)
-            h2 = _empty(M, D, like=h)
-            gemm(M, D, D, cx, D, Wo_f, ldo_f, h2, D, b_layout=lay_o, bias=bo, out_drop=plan.spec(site_res1(i), D),
-                 residual=(h, D), bf16=plan.bf16)
-            st2 = _empty(M, 2, like=h)
-            if a16:
-                u2 = torch.empty(M, D, device=h.device, dtype=torch.bfloat16)
-                ops.layernorm_fwd(h2, D, ln2w, ln2b, None, D, st2, M, D, y16=u2, ldy16=D)
-            else:
-                u2 = _empty(M, D, like=h)
-                ops.layernorm_fwd(h2, D, ln2w, ln2b, u2, D, st2, M, D)
-            # gelu(fc) is only ever read by the c_proj GEMM: in bf16 mode it is written as bf16.  The pre-activation
-            # the backward differentiates GELU at is bf16 too (TECM_IO_PRE_BF16: rounded BEFORE the activation, as
-            # autocast's bf16 Linear output is) -- a third less to write here, half as much to read back there.
-            f16 = b16 and Wfc_f.dtype == torch.bfloat16 and Wpr_f.dtype == torch.bfloat16
-            a = torch.empty(M, F4, device=h.device, dtype=torch.bfloat16 if f16 and PRE16 else torch.float32)
-            f = torch.empty(M, F4, device=h.device, dtype=torch.bfloat16 if f16 else torch.float32)
-            gemm(M, F4, D, u2, D, Wfc_f, ldfc_f, f, F4, b_layout=lay_fc, bias=bfc, preact=(a, F4), act=ACT_GELU_TANH,
-                 bf16=plan.bf16)
-            h3 = _empty(M, D, like=h)
-            gemm(M, D, F4, f, F4, Wpr_f, ldpr_f, h3, D, b_layout=lay_pr, bias=bpr, out_drop=plan.spec(site_res2(i), D),
-                 residual=(h2, D), bf16=plan.bf16)
-            del cx, u2, f                                   # forward-only buffers: the backward needs none of them
-            saved += [h, u_s, ud_s, st1, wcat, qkv, h2, st2, a]
+            lp = params[i * GPT2StackFn.PER_LAYER:(i + 1) * GPT2StackFn.PER_LAYER]
+            # level 0 keeps everything the block's backward reads; level >= 1 and the lean forward (no backward will run) free
+            # each buffer once the launch that last reads it is queued -- the recompute keeps the block's input h alone
+            h3, acts, wk = GPT2StackFn._block_fwd(h, i, lp, plan, B, T, N, keep=plan.keep and level == 0)
+            ctx_lAT.append(wk[3])
+            ctx_gen.append(wk[4])
+            if acts is not None:
+                u_s, ud_s, st1, qkv, h2, st2, a = acts
+                saved += [h, u_s, ud_s, st1, wk[0], qkv, h2, st2, a]
+                del acts, u_s, ud_s, st1, qkv, h2, st2, a
+            elif plan.keep:
+                saved.append(h)
+                ctx_wk.append(wk)
             h = h3
         lnfw, lnfb = params[n_layers * GPT2StackFn.PER_LAYER:]
         stf = _empty(M, 2, like=h)
@@ -765,8 +751,112 @@ class GPT2StackFn(torch.autograd.Function):
         ctx.save_for_backward(h, stf, *saved, *params)
         ctx.lAT16 = ctx_lAT
         ctx.kext_gen = ctx_gen
+        ctx.wk = ctx_wk
+        ctx.level = level
         ctx.meta = (B, T, N, D, n_layers, plan, len(saved))
         return out
+
+    @staticmethod
+    def _block_fwd(h, i: int, lp, plan: DropPlan, B: int, T: int, N: int, wk=None, out: bool = True, keep: bool = True):
+        """GPT2Block i on h (M rows of D) -> (h3, acts, wk).  acts = (u, ud, st1, qkv, h2, st2, a), what the block's backward
+        reads, or None (keep=False: each buffer is dropped as soon as the launch that last reads it is queued).  wk = (wcat,
+        wcatT, lora_A bf16, lora_A^T bf16, generation): the LoRA-folded c_attn operands.  The recompute of the backward
+        passes the forward's wk (no second lora_fold: the same operands, the same generation) and out=False (the block's
+        output h3 -- the next block's saved input -- is not formed again); every other launch is the forward's, with the
+        forward's arguments and dropout plan, so the rebuilt tensors are the forward's bit for bit."""
+        (ln1w, ln1b, Wqkv, bqkv, lA, lB, Wo, bo, ln2w, ln2b, Wfc, bfc, Wpr, bpr) = lp
+        D = h.shape[-1]
+        M = B * T * N
+        KE = D + LORA_R
+        F3, F4 = Wqkv.shape[1], Wfc.shape[1]
+        b16 = int(plan.bf16) == ops.PREC_BF16           # bf16 mode: weights and GEMM-only activations live in HBM as bf16
+        wcatT = _frozen_copy(Wqkv, "kext_nk16" if b16 else "kext_nk32") if wk is None else wk[1]   # [ W^T | (alpha/r) B ]
+        Wo_f, ldo_f, lay_o = _fwd_weight(Wo, D, D, plan.bf16)
+        Wfc_f, ldfc_f, lay_fc = _fwd_weight(Wfc, D, F4, plan.bf16)
+        Wpr_f, ldpr_f, lay_pr = _fwd_weight(Wpr, F4, D, plan.bf16)
+        # Activations whose ONLY reader is a bf16 GEMM are written as bf16 by their producer (rounded once there
+        # instead of in that GEMM's loader: bit-identical, half the bytes both ways): LN1's output for c_attn, the
+        # attention context for attn.c_proj, LN2's output for c_fc, gelu(c_fc) for mlp.c_proj.
+        a16 = b16 and all(w is not None and w.dtype == torch.bfloat16 for w in (wcatT, Wo_f, Wfc_f, Wpr_f))
+        st1 = _empty(M, 2, like=h)
+        lspec = plan.spec(site_lora(i), KE)
+        lA16 = lAT16 = None
+        if a16:
+            # bf16 mode: [ LN1(h) | z ] only ever feeds bf16 contractions, so it exists as bf16 alone (u16); the LoRA
+            # branch's input drop(LN1(h)) -- what autocast casts in front of lora_A -- is a second bf16 output of the
+            # LayerNorm kernel (u16d), read by the LoRA-A GEMM here and by its weight gradient in the backward, and z
+            # is written straight into u16's last 32 columns as bf16
+            u = None
+            u16 = torch.empty(M, KE, device=h.device, dtype=torch.bfloat16)
+            u16d = torch.empty(M, D, device=h.device, dtype=torch.bfloat16) if lspec is not None else None
+            ops.layernorm_fwd(h, D, ln1w, ln1b, None, KE, st1, M, D, y16=u16, ldy16=KE, y16d=u16d, ldy16d=D, drop16d=lspec)
+            a_lora, ld_lora = (u16d, D) if u16d is not None else (u16, KE)
+            # lora_A rounded (and transposed for its d-input contraction in the backward): both operands bf16 tensors
+            lA16, lAT16 = ops.weight_bf16(lA, same=True, transposed=True) if wk is None else wk[2:4]
+            gemm(M, LORA_R, D, a_lora, ld_lora, lA16, D, u16, KE, c_off=D, bf16=plan.bf16)
+            del a_lora
+        else:
+            u = _empty(M, KE, like=h)                   # [ LN1(h) | z = drop(LN1(h)) A^T ]  (fp32: the LoRA gradients read it)
+            u16 = u16d = None
+            ops.layernorm_fwd(h, D, ln1w, ln1b, u, KE, st1, M, D)
+            gemm(M, LORA_R, D, u, KE, lA, D, u, KE, c_off=D, a_drop=lspec, bf16=plan.bf16)
+        if not keep:
+            u16d = None
+        if wk is None:
+            # [ W ; (alpha/r) B^T ]  K-extended c_attn, backward operand ([KE][F3]) and forward operand ([F3][KE]): the
+            # frozen 768 x 2304 part of both is cached per parameter version (_frozen_copy), ONE launch refreshes the 32
+            # LoRA rows / columns of both from lora_B.  (The buffers are the cache's: they are rewritten by the next
+            # forward of this layer, normally after the backward that reads `wcat` has run.  The rewrite goes through a raw
+            # pointer, behind torch's version counter, so every fold bumps a generation number of the buffer and the backward
+            # checks it: a second forward of the same frozen base weight with an outstanding backward -- two adapters over
+            # one base, retain_graph across an optimizer step -- raises instead of differentiating against the wrong B.)
+            wcat = _frozen_copy(Wqkv, "kext_kn16" if b16 else "kext_kn32")
+            ops.lora_fold(lB.detach(), LORA_SCALE, wcat, wcatT, D)
+            _KEXT_GEN[wcat.data_ptr()] = _KEXT_GEN.get(wcat.data_ptr(), 0) + 1
+            wk = (wcat, wcatT, lA16, lAT16, _KEXT_GEN[wcat.data_ptr()])
+        # bf16 mode: qkv is written as bf16 by the c_attn GEMM (what a Linear's output is under autocast) and read as
+        # such by the attention kernels, forward and backward: 644 -> 322 MB per layer, three times over
+        qkv = torch.empty(M, F3, device=h.device, dtype=torch.bfloat16 if (a16 and QKV16) else torch.float32)
+        gemm(M, F3, KE, u16 if a16 else u, KE, wcatT, KE, qkv, F3, b_layout=B_NK, bias=bqkv, bf16=plan.bf16)
+        if not keep:
+            u = u16 = None
+        cx = torch.empty(M, D, device=h.device, dtype=torch.bfloat16 if a16 else torch.float32)
+        aspec = plan.spec(site_attn(i), 1)
+        ops.attention_fwd(qkv, cx, B, T, N, GPT_HEADS, D, aspec)
+        if not keep:
+            qkv = None
+        h2 = _empty(M, D, like=h)
+        gemm(M, D, D, cx, D, Wo_f, ldo_f, h2, D, b_layout=lay_o, bias=bo, out_drop=plan.spec(site_res1(i), D),
+             residual=(h, D), bf16=plan.bf16)
+        if not keep:
+            cx = None
+        st2 = _empty(M, 2, like=h)
+        if a16:
+            u2 = torch.empty(M, D, device=h.device, dtype=torch.bfloat16)
+            ops.layernorm_fwd(h2, D, ln2w, ln2b, None, D, st2, M, D, y16=u2, ldy16=D)
+        else:
+            u2 = _empty(M, D, like=h)
+            ops.layernorm_fwd(h2, D, ln2w, ln2b, u2, D, st2, M, D)
+        # gelu(fc) is only ever read by the c_proj GEMM: in bf16 mode it is written as bf16.  The pre-activation
+        # the backward differentiates GELU at is bf16 too (TECM_IO_PRE_BF16: rounded BEFORE the activation, as
+        # autocast's bf16 Linear output is) -- a third less to write here, half as much to read back there.
+        f16 = b16 and Wfc_f.dtype == torch.bfloat16 and Wpr_f.dtype == torch.bfloat16
+        a = torch.empty(M, F4, device=h.device, dtype=torch.bfloat16 if f16 and PRE16 else torch.float32)
+        f = torch.empty(M, F4, device=h.device, dtype=torch.bfloat16 if f16 else torch.float32)
+        gemm(M, F4, D, u2, D, Wfc_f, ldfc_f, f, F4, b_layout=lay_fc, bias=bfc, preact=(a, F4), act=ACT_GELU_TANH,
+             bf16=plan.bf16)
+        if not keep:
+            u2 = a = None
+        h3 = None
+        if out:
+            h3 = _empty(M, D, like=h)
+            gemm(M, D, F4, f, F4, Wpr_f, ldpr_f, h3, D, b_layout=lay_pr, bias=bpr, out_drop=plan.spec(site_res2(i), D),
+                 residual=(h2, D), bf16=plan.bf16)
+        del cx, u2, f                                   # forward-only buffers: the backward needs none of them
+        if not keep:
+            return h3, None, wk
+        u_s, ud_s = (u16, (u16d if u16d is not None else h.new_empty(0))) if a16 else (u, h.new_empty(0))
+        return h3, (u_s, ud_s, st1, qkv, h2, st2, a), wk
 
     @staticmethod
     def backward(ctx, dout):
@@ -803,11 +893,21 @@ class GPT2StackFn(torch.autograd.Function):
         for i in reversed(range(n_layers)):
             (ln1w, ln1b, Wqkv, bqkv, lA, lB, Wo, bo, ln2w, ln2b, Wfc, bfc, Wpr,
              bpr) = params[i * GPT2StackFn.PER_LAYER:(i + 1) * GPT2StackFn.PER_LAYER]
-            h, u, ud, st1, wcat, qkv, h2, st2, a = saved[i * 9:(i + 1) * 9]
+            if ctx.level == 0:
+                h, u, ud, st1, wcat, qkv, h2, st2, a = saved[i * 9:(i + 1) * 9]
+            else:
+                h, wcat = saved[i], ctx.wk[i][0]
             if _KEXT_GEN.get(wcat.data_ptr()) != ctx.kext_gen[i]:
                 raise _lib_error(f"GPT-2 block {i}: the K-extended c_attn operand [W ; 2 B^T] was rewritten by a later forward "
                                 "of the same frozen base weight before this backward ran (shared cache buffer); run each "
                                 "forward's backward before the next forward of that layer")
+            if ctx.level:
+                # recompute: block i's forward again from its saved input, with the forward's folded operands and dropout plan
+                # (bit-identical tensors), just before block i's backward; they are dropped before block i-1 is rebuilt
+                _, acts, _ = GPT2StackFn._block_fwd(h, i, params[i * GPT2StackFn.PER_LAYER:(i + 1) * GPT2StackFn.PER_LAYER],
+                                                    plan, B, T, N, wk=ctx.wk[i], out=False)
+                u, ud, st1, qkv, h2, st2, a = acts
+                del acts
             F3, F4 = Wqkv.shape[1], Wfc.shape[1]
             # MLP:  h3 = h2 + drop(gelu(u2 Wfc + b) Wpr + b)
             Wpr_b, Wfc_b = _bwd_weight(Wpr, plan.bf16), _bwd_weight(Wfc, plan.bf16)
@@ -874,6 +974,8 @@ class GPT2StackFn(torch.autograd.Function):
             pgrads[base + 0], pgrads[base + 1] = dg1, db1
             pgrads[base + 4], pgrads[base + 5] = dlA, dlB
             pgrads[base + 8], pgrads[base + 9] = dg2, db2
+            if ctx.level:                                 # the rebuilt block and its gradients' working set
+                del u, ud, st1, qkv, h2, st2, a, du2, dh2, dh2m, dcx, dqkv, du, dzA
         pg = [g if ctx.needs_input_grad[3 + j] else None for j, g in enumerate(pgrads)]
         return (dh.view(B, T, N, D), None, None, *pg, dlnfw, dlnfb)
 

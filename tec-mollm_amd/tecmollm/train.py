@@ -176,9 +176,12 @@ class TrainStep:
         from . import devcheck, ops
         from ._lib import check, lib, stream_ptr
         tf_uniform = time_features.dim() == 4 and time_features.stride(2) == 0 and time_features.shape[2] > 1
+        # the recompute level the forward will pick (tecmollm/memory.py): a recording replays that level's launches
+        level_of = getattr(self.model, "recompute_level_for", None)
+        level = level_of(x.shape[0], self.model.precision_code(), True) if level_of is not None else 0
         key = (tuple(x.shape), tuple(time_features.shape), tf_uniform, tuple(y.shape), str(y.dtype), self.model.training,
                torch.is_autocast_enabled("cuda"), str(torch.get_autocast_dtype("cuda")), self.accumulation_steps,
-               id(edge_index))
+               id(edge_index), level)
         rec = self._graphs.get(key)
         if rec is None:                                # first sight of this configuration: a plain step, and the warm-up
             self._graphs[key] = False

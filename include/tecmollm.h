@@ -33,7 +33,7 @@ extern "C" {
 #define TECM_E_LAUNCH (-3)     /* hipGetLastError() != hipSuccess after the launch       */
 #define TECM_E_LDS (-4)        /* problem does not fit the 160 KiB LDS budget            */
 
-#define TECM_ABI_VERSION 17
+#define TECM_ABI_VERSION 18
 int tecm_abi_version(void);
 /* Human-readable text for the last error on this thread (host pointer, never NULL). */
 const char* tecm_last_error(void);
@@ -537,6 +537,46 @@ typedef struct {
   float* x_out; float* tf_out; float* y_out;
 } TecmWindowBatch;
 int tecm_window_batch(const TecmWindowBatch* w, void* stream);
+
+/* (5) per-window baseline forecasts straight from the device-resident series (the second half of the reference's test.py):
+ * for window b with start a = starts[b] (already multiplied by the dataset stride), node n < N and horizon h < L_out, with
+ * x(t) = X[t*N*C + n*C + channel]:
+ *   TECM_BASELINE_MEAN      out[b,h,n] = (((x(a) + x(a+1)) + ...) + x(a+L_in-1)) / (float)L_in -- the historical average of
+ *                           get_baseline_predictions (test.py:57-62).  fp32 adds in ascending time order, then ONE IEEE fp32
+ *                           division: the bits numpy's np.mean(x_window[:, :, :, 0:1], axis=0) returns for an fp32 window.
+ *   TECM_BASELINE_LAST      out[b,h,n] = x(a + L_in - 1)                                    (persistence; not in the reference)
+ *   TECM_BASELINE_PERIODIC  out[b,h,n] = x(a + L_in - period + (h mod period))              (the same slot one period ago: with
+ *                           period = 12 two-hourly steps, yesterday; not in the reference).  Needs L_in >= period > 0.
+ * All three read channel `channel` of the feature-scaled X as it is, as the reference's baseline does, although the targets
+ * they are scored against carry the target scaler.
+ * out is addressed as out[b*o_stride_b + h*o_stride_h + n*o_stride_n] (element strides).  o_stride_h may be 0 for MEAN and
+ * LAST (every horizon holds the same value: it is then written once -- the (B, L_out, N, 1) forecast as a stride-0 view);
+ * PERIODIC with L_out > 1 needs o_stride_h != 0.  X (T, N*C) fp32, starts (B) int64 on the device; windows are range-checked
+ * on the host when starts_host_check is given (same values, host memory) and a window outside [0, T - L_in] that reaches
+ * the kernel is written as NaN, never read. */
+enum { TECM_BASELINE_MEAN = 0, TECM_BASELINE_LAST = 1, TECM_BASELINE_PERIODIC = 2 };
+typedef struct {
+  const float* X; const int64_t* starts;
+  const int64_t* starts_host_check;
+  int64_t T;
+  int32_t N, C, channel, L_in, L_out, B, mode, period;
+  float* out; int64_t o_stride_b, o_stride_h, o_stride_n;
+} TecmWindowBaseline;
+int tecm_window_baseline(const TecmWindowBaseline* w, void* stream);
+
+/* (6) HistoricalAverage.fit (src/models/baselines.py:13-33): the mean of a series per node and time-of-day slot,
+ *   means[n*n_slots + s] = sum over { t < T : slot[t] == s } of x[t*stride_t + n*stride_n]  /  counts[s]
+ * x fp32 addressed by element strides ((T, N) data, or one channel of (T, N*C) in place), slot (T) int32 on the device
+ * (values outside [0, n_slots) belong to no slot), means (N, n_slots) and counts (n_slots) doubles.  Sums are fp64 in
+ * ascending time order inside four fixed quarters of T that are then added as (q0 + q1) + (q2 + q3); no atomics, so two
+ * launches return identical bits.  An empty slot yields NaN (numpy's mean of an empty selection). */
+typedef struct {
+  const float* x; int64_t stride_t, stride_n;
+  const int32_t* slot;
+  int64_t T; int32_t N, n_slots;
+  double* means; double* counts;
+} TecmSlotMean;
+int tecm_slot_mean(const TecmSlotMean* m, void* stream);
 
 #ifdef __cplusplus
 }

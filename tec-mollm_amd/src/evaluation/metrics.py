@@ -87,6 +87,16 @@ class HorizonMetrics:
                         clip=1 if self.scaler is not None else 0, stats=self.stats.data_ptr())
         check(lib().tecm_metrics_accumulate(C.byref(m), stream_ptr()), "tecm_metrics_accumulate")
 
+    def merge_(self, group=None) -> "HorizonMetrics":
+        """Sum the (H, 8) statistics over the ranks of `group` (None: the default process group) with one all-reduce,
+        in place.  Every statistic is a plain sum over (sample, node) pairs, so ranks that each fed their own shard of a
+        split end up with the statistics -- and hence the metrics -- of the whole split; the reference lets rank 0
+        report its own shard only (train.py:153-166, :389-410).  Without an initialised process group this is a no-op."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            dist.all_reduce(self.stats, op=dist.ReduceOp.SUM, group=group)
+        return self
+
     def compute(self) -> Dict[str, object]:
         st = self.stats.cpu().numpy()
         per = []

@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TECM_LIB", os.path.join(_HERE, "libtecmollm_hip.so"))   # override for experiments
-ABI_VERSION = 17
+ABI_VERSION = 18
 
 c_f32p = C.c_void_p
 
@@ -115,6 +115,26 @@ class TecmWindowBatch(C.Structure):
         ("x_out", c_f32p), ("tf_out", c_f32p), ("y_out", c_f32p),
     ]
 
+
+class TecmWindowBaseline(C.Structure):
+    _fields_ = [
+        ("X", c_f32p), ("starts", C.c_void_p), ("starts_host_check", C.c_void_p),
+        ("T", C.c_int64),
+        ("N", C.c_int32), ("C", C.c_int32), ("channel", C.c_int32), ("L_in", C.c_int32), ("L_out", C.c_int32),
+        ("B", C.c_int32), ("mode", C.c_int32), ("period", C.c_int32),
+        ("out", c_f32p), ("o_stride_b", C.c_int64), ("o_stride_h", C.c_int64), ("o_stride_n", C.c_int64),
+    ]
+
+
+class TecmSlotMean(C.Structure):
+    _fields_ = [
+        ("x", c_f32p), ("stride_t", C.c_int64), ("stride_n", C.c_int64),
+        ("slot", C.c_void_p),
+        ("T", C.c_int64), ("N", C.c_int32), ("n_slots", C.c_int32),
+        ("means", C.c_void_p), ("counts", C.c_void_p),
+    ]
+
+
 class TecmConvDx(C.Structure):
     _fields_ = [("dy", C.c_void_p), ("wpack", C.c_void_p), ("dinp", c_f32p),
                 ("B", C.c_int32), ("Lc", C.c_int32), ("N", C.c_int32), ("Cout", C.c_int32), ("ld_in", C.c_int32),
@@ -136,6 +156,7 @@ class TecmConvFwd(C.Structure):
 
 TECM_NORM_BLOCKS = 512
 TECM_METRIC_STATS = 8
+TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
 
 
 EXPORTS = {
@@ -209,6 +230,8 @@ EXPORTS = {
     "tecm_seed_advance": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "tecm_metrics_accumulate": (C.c_int, [C.POINTER(TecmMetrics), C.c_void_p]),
     "tecm_window_batch": (C.c_int, [C.POINTER(TecmWindowBatch), C.c_void_p]),
+    "tecm_window_baseline": (C.c_int, [C.POINTER(TecmWindowBaseline), C.c_void_p]),
+    "tecm_slot_mean": (C.c_int, [C.POINTER(TecmSlotMean), C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

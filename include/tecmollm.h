@@ -33,7 +33,7 @@ extern "C" {
 #define TECM_E_LAUNCH (-3)     /* hipGetLastError() != hipSuccess after the launch       */
 #define TECM_E_LDS (-4)        /* problem does not fit the 160 KiB LDS budget            */
 
-#define TECM_ABI_VERSION 18
+#define TECM_ABI_VERSION 19
 int tecm_abi_version(void);
 /* Human-readable text for the last error on this thread (host pointer, never NULL). */
 const char* tecm_last_error(void);
@@ -138,6 +138,11 @@ int32_t tecm_gemm_tn_splits(int64_t M, int64_t N, int64_t K);
  * M x N result on this device: the height whose tile count wastes least of the last round of CUs (csrc/gemm_bf16_p8.hip).
  * Exposed so that a caller's per-kernel accounting can name the instantiation a call runs on. */
 int tecm_p8_rows(int64_t M, int64_t N);
+/* Name of the contraction kernel (template arguments included, e.g. "gemm_kernel<0,0,4,4,128,false,false,128>") that this
+ * thread's most recent successful tecm_gemm_* call launched; the split-K reducer and the erf-GELU pass behind it are not
+ * reported.  "" before the first call, unspecified after a failed one.  Host pointer, valid for the life of the library.
+ * Pure host function. */
+const char* tecm_gemm_last_kernel(void);
 
 /* ------------------------------------------------------------------ stage a-1..a-3 (fused)
  * SpatioTemporalEmbedding.forward (modules.py:230-266) + GATv2Conv (modules.py:329-336,:356)
@@ -215,6 +220,10 @@ int tecm_spatial_bwd2_blocks(const TecmSpatial* d);
 int tecm_spatial_bwd2(const TecmSpatial* d, const TecmSpatialGrads* g, float* ws, void* stream);
 /* Number of blocks (= rows of TecmSpatialGrads.partials) tecm_spatial_bwd will launch for `d`; negative = TECM_E_*. */
 int tecm_spatial_bwd_blocks(const TecmSpatial* d);
+/* Dynamic LDS bytes tecm_spatial_fwd / tecm_spatial_bwd need for a tiling (TecmSpatial::win_max, tile_nodes, tile_edges_max,
+ * Demb); the launchers refuse with TECM_E_LDS above 160 KiB, so a caller picks its tile size with these.  Pure host functions. */
+int64_t tecm_spatial_fwd_lds_bytes(int32_t win_max, int32_t tile_nodes, int32_t tile_edges_max);
+int64_t tecm_spatial_bwd_lds_bytes(int32_t win_max, int32_t tile_nodes, int32_t tile_edges_max, int32_t Demb);
 
 /* ------------------------------------------------------------------ stage a-4 normalisation
  * nn.GroupNorm(1, C) + nn.GELU() (modules.py:28-29) for the three parallel branches at once.
@@ -234,9 +243,13 @@ int tecm_spatial_bwd_blocks(const TecmSpatial* d);
  * the rounded y it produced (TecmConvFwd::stats); the norm + GELU then is elementwise over the time steps act keeps. */
 #define TECM_GN_STATS_GIVEN 8
 int tecm_gn_y16_supported(int32_t L, int32_t N, int32_t Cout);
+/* 1 when BOTH directions have a register-resident kernel (the only fp32-y kernels that take a bf16 act / dact / dy, and the
+ * only ones that serve act_stride > 1): L * 3*Cout/4 quads in whole rounds of 4 or 8 waves, at most 9 per lane.  Pure host
+ * function. */
+int tecm_gn_reg_supported(int32_t L, int32_t N, int32_t Cout);
 /* act_stride s >= 1: only the time steps t % s == 0 are written, into a COMPACT (B, ceil(L / s), N, CT) tensor -- the
  * stride-s 1x1 conv behind the block (modules.py:36-41) reads nothing else; the statistics cover every step.  s > 1 is
- * served by the register-resident kernels only (TECM_E_ARG otherwise: callers ask tecm_gn_reg_ok first). */
+ * served by the register-resident kernels only (TECM_E_ARG otherwise: callers ask tecm_gn_reg_supported first). */
 int tecm_groupnorm_gelu_fwd(const void* y, const float* gamma, const float* beta, void* act,
                             float* stats, int32_t B, int32_t L, int32_t N, int32_t Cout, float eps,
                             int32_t io_bf16, int32_t act_stride, void* stream);
@@ -394,6 +407,9 @@ int tecm_conv_dx_f32(const TecmConvDx* p, void* stream);
  * the shapes these kernels refuse to the window-view GEMMs (tecm_gemm_*) instead of failing with TECM_E_LDS. */
 int tecm_conv_fwd_supported(int32_t Lc, int32_t Cout, int32_t ld_in, int32_t f32);
 int tecm_conv_dx_supported(int32_t Lc, int32_t Cout, int32_t ld_in, int32_t f32);
+/* 1 when one forward tile holds a whole sequence of Lc steps -- the condition for TecmConvFwd::stats -- else 0.  Pure host
+ * function. */
+int tecm_conv_fwd_stats_supported(int32_t Lc);
 
 /* Weight gradient of the same three Conv1d in ONE launch pair, bf16 mode (replaces the three split-K window GEMMs
  * dY^T . window(inp) behind nn.Conv1d's autograd, modules.py:27,36):
@@ -420,6 +436,8 @@ int tecm_huber_fwd_bwd_strided(const float* pred, const int64_t* pred_strides /*
                                int32_t N, float delta, float grad_scale, float* workspace /* >= 1024 */, void* stream);
 
 int64_t tecm_conv_dw_workspace(int32_t Cout, int32_t ld_in, int32_t num_blocks);
+/* 1 when tecm_conv_dw_{bf16,f32} serve the shape (the table the launcher itself refuses from), else 0.  Pure host function. */
+int tecm_conv_dw_supported(int32_t Lc, int32_t Cout, int32_t ld_in);
 int tecm_conv_dw_bf16(const TecmConvDw* p, void* stream);
 /* The same in exact fp32 (BASELINE configs[1]): inp and dy fp32, v_mfma_f32_32x32x2_f32. */
 int tecm_conv_dw_f32(const TecmConvDw* p, void* stream);

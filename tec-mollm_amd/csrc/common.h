@@ -30,6 +30,10 @@ void tecm_set_error(const char* fmt, ...);
     }                                                                               \
   } while (0)
 
+// Name of the contraction kernel this thread's GEMM entry points launched last (tecm_gemm_last_kernel): every launch site
+// stores it next to its launch -- a string literal, or a static built once per template instance.
+extern thread_local const char* tecm_gemm_kernel;
+
 static inline bool tecm_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // ------------------------------------------------------------------ counter-based dropout mask

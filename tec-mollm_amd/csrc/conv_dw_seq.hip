@@ -404,26 +404,36 @@ extern "C" int64_t tecm_conv_dw_workspace(int32_t Cout, int32_t ld_in, int32_t n
   return (int64_t)f * (num_blocks / f > 0 ? num_blocks / f : 1) * ks * tecm_convdw::NTAP * 32 * ncib * 32 * cpb;
 }
 
+// The instances that are built: X(ld_in, Cout, PD).  PD = register sets in flight of the bf16 kernel: two where they fit
+// WITHOUT spilling (a spilled register with a hand-issued load pending would be stored before the data has landed;
+// __graft_entry__.build() checks ScratchSize of every instantiation).  The fp32 kernel is bound by the matrix cores (11 us
+// of MFMA per tile): one set is plenty.
+#define TECM_DW_SHAPES(X) X(64, 128, 2) X(24, 64, 2) X(64, 64, 2) X(24, 128, 1 /* not a shape of the reference model */)
+
+// 1 when tecm_conv_dw_{bf16,f32} serve sequences of Lc steps with these channel counts, else 0
+extern "C" int tecm_conv_dw_supported(int32_t Lc, int32_t Cout, int32_t ld_in) {
+  if (Lc <= 0 || Lc % 4 != 0) return 0;
+#define TECM_DW_CASE(LD, CO, PD) \
+  if (ld_in == LD && Cout == CO) return 1;
+  TECM_DW_SHAPES(TECM_DW_CASE)
+#undef TECM_DW_CASE
+  return 0;
+}
+
 static int conv_dw_launch(const TecmConvDw* p, void* stream, bool f32, const char* who) {
   TECM_REQUIRE(p && p->inp && p->dy && p->workspace && p->dw3 && p->dw5 && p->dw7, TECM_E_ARG, "%s: null pointer", who);
-  TECM_REQUIRE(p->B > 0 && p->N > 0 && p->Lc > 0 && p->Lc % 4 == 0, TECM_E_ARG,
-               "%s: the sequence length must be a multiple of 4 (got %d)", who, p->Lc);
+  TECM_REQUIRE(p->B > 0 && p->N > 0 && tecm_conv_dw_supported(p->Lc, p->Cout, p->ld_in), TECM_E_ARG,
+               "%s: built for sequence lengths that are multiples of 4 and ld_in in {24, 64} x Cout in {64, 128} (got %d, %d, %d)",
+               who, p->Lc, p->ld_in, p->Cout);
   TECM_REQUIRE(p->Cin > 0 && p->Cin <= p->ld_in && p->num_blocks > 0, TECM_E_ARG, "%s: bad Cin / num_blocks", who);
   TECM_REQUIRE(tecm_aligned(p->inp, 16) && tecm_aligned(p->dy, 16), TECM_E_ALIGN, "%s: 16-byte aligned tensors", who);
   hipStream_t st = (hipStream_t)stream;
-  // PD = register sets in flight: two where they fit WITHOUT spilling (a spilled register with a hand-issued load pending
-  // would be stored before the data has landed; __graft_entry__.build() checks ScratchSize of every instantiation).  The
-  // fp32 kernel is bound by the matrix cores (11 us of MFMA per tile): one set is plenty.
-#define TECM_DW_CASE(LD, CO, PD)                                                              \
-  if (p->ld_in == LD && p->Cout == CO)                                                        \
-    return f32 ? tecm_convdw::launch<LD, CO, 1, true>(p, st) : tecm_convdw::launch<LD, CO, PD, false>(p, st)
-  TECM_DW_CASE(64, 128, 2);
-  TECM_DW_CASE(24, 64, 2);
-  TECM_DW_CASE(64, 64, 2);
-  TECM_DW_CASE(24, 128, 1);                                  // (not a shape of the reference model)
+#define TECM_DW_CASE(LD, CO, PD)        \
+  if (p->ld_in == LD && p->Cout == CO) \
+    return f32 ? tecm_convdw::launch<LD, CO, 1, true>(p, st) : tecm_convdw::launch<LD, CO, PD, false>(p, st);
+  TECM_DW_SHAPES(TECM_DW_CASE)
 #undef TECM_DW_CASE
-  TECM_REQUIRE(false, TECM_E_ARG, "%s: built for ld_in in {24, 64} x Cout in {64, 128} (got %d, %d)", who, p->ld_in, p->Cout);
-  return TECM_E_ARG;
+  return TECM_E_ARG;                                         // not reached: every supported shape is in the table
 }
 extern "C" int tecm_conv_dw_bf16(const TecmConvDw* p, void* stream) { return conv_dw_launch(p, stream, false, "tecm_conv_dw_bf16"); }
 extern "C" int tecm_conv_dw_f32(const TecmConvDw* p, void* stream) { return conv_dw_launch(p, stream, true, "tecm_conv_dw_f32"); }

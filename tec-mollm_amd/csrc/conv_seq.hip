@@ -886,6 +886,9 @@ extern "C" int tecm_conv_fwd_supported(int32_t Lc, int32_t Cout, int32_t ld_in, 
   return conv_fwd_lds(Lc, ld_in, f32 != 0, nullptr, nullptr) <= 64 * 1024 ? 1 : 0;
 }
 
+// 1 when one forward tile holds a whole sequence of Lc steps, so that tecm_conv_fwd_bf16 can compute TecmConvFwd::stats, else 0
+extern "C" int tecm_conv_fwd_stats_supported(int32_t Lc) { return Lc > 0 && Lc <= 8 * tecm_convseq::MAXT ? 1 : 0; }
+
 static int conv_fwd_launch(const TecmConvFwd* p, void* stream, bool f32, const char* who) {
   using namespace tecm_convseq;
   TECM_REQUIRE(p && p->inp && p->wpack && p->bias && p->y, TECM_E_ARG, "%s: null pointer", who);
@@ -908,7 +911,7 @@ static int conv_fwd_launch(const TecmConvFwd* p, void* stream, bool f32, const c
   const size_t lds = conv_fwd_lds(p->Lc, p->ld_in, f32, &a.pitch, &a.TC);
   a.nchunk = (p->Lc + a.TC - 1) / a.TC;
   a.nblk = (p->N + NB - 1) / NB;
-  TECM_REQUIRE(!a.stats || (a.y16 && !f32 && a.nchunk == 1 && p->eps > 0.f), TECM_E_ARG,
+  TECM_REQUIRE(!a.stats || (a.y16 && !f32 && tecm_conv_fwd_stats_supported(p->Lc) && p->eps > 0.f), TECM_E_ARG,
                "%s: GroupNorm statistics come with a bf16 y and sequences of at most %d steps (one tile per sequence)", who, a.TC);
   TECM_REQUIRE(lds <= 64 * 1024, TECM_E_LDS, "%s: %zu B of LDS per tile", who, lds);
   // units (kernel size j, 32-channel block), longest first, each to the least loaded wave

@@ -1119,6 +1119,7 @@ int tecm_gemm16_dma_try(const TecmGemm& g, hipStream_t st) {
     const int wtm = (int)((g.M + DBM - 1) / DBM), wtn = (int)((g.N + DBN - 1) / DBN);
     hipLaunchKernelGGL(gemm_bf16_dma_kernel, dim3((unsigned)(wtm * wtn)), dim3(DNTH), 0, st, g, wtm, wtn);
     TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma-window");
+    tecm_gemm_kernel = "gemm_bf16_dma_kernel";
     return 1;
   }
   // round 5: the eight-phase geometry (gemm_bf16_p8.hip) wherever it is eligible (it declines n-tiles that are mostly
@@ -1132,6 +1133,7 @@ int tecm_gemm16_dma_try(const TecmGemm& g, hipStream_t st) {
     const int t2m = (int)((g.M + D2M - 1) / D2M), t2n = (int)((g.N + D2N - 1) / D2N);
     hipLaunchKernelGGL(gemm_bf16_dma2_kernel, dim3((unsigned)(t2m * t2n)), dim3(D2TH), 0, st, g, t2m, t2n);
     TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma2");
+    tecm_gemm_kernel = "gemm_bf16_dma2_kernel";
     return 1;
   }
   const int tiles_m = (int)((g.M + DBM - 1) / DBM);
@@ -1151,9 +1153,11 @@ int tecm_gemm16_dma_try(const TecmGemm& g, hipStream_t st) {
       if (sel[0] == '6') {
         const int t6m = (int)((g.M + 255) / 256), t6n = (int)((g.N + 127) / 128);
         hipLaunchKernelGGL((gemm_bf16_dma6_kernel<256, 128, 2, 2>), dim3((unsigned)(t6m * t6n)), dim3(256), 0, st, g, t6m, t6n);
+        tecm_gemm_kernel = "gemm_bf16_dma6_kernel<256,128,2,2>";
       } else {
         const int t6m = (int)((g.M + 127) / 128), t6n = (int)((g.N + 255) / 256);
         hipLaunchKernelGGL((gemm_bf16_dma6_kernel<128, 256, 1, 4>), dim3((unsigned)(t6m * t6n)), dim3(256), 0, st, g, t6m, t6n);
+        tecm_gemm_kernel = "gemm_bf16_dma6_kernel<128,256,1,4>";
       }
       TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma6");
       return 1;
@@ -1173,10 +1177,12 @@ int tecm_gemm16_dma_try(const TecmGemm& g, hipStream_t st) {
         const int tm288 = (int)((g.M + 287) / 288);
         hipLaunchKernelGGL(gemm_bf16_dma5w_kernel, dim3((unsigned)(tm288 * tiles_n)), dim3(D3TH), 0, st, g, tm288, tiles_n);
         TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma5w");
+        tecm_gemm_kernel = "gemm_bf16_dma5w_kernel";
         return 1;
       }
       hipLaunchKernelGGL(gemm_bf16_dma5_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(D3TH), 0, st, g, tiles_m, tiles_n);
       TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma5");
+      tecm_gemm_kernel = "gemm_bf16_dma5_kernel";
       return 1;
     }
   }
@@ -1184,14 +1190,17 @@ int tecm_gemm16_dma_try(const TecmGemm& g, hipStream_t st) {
   if (ring) {
     hipLaunchKernelGGL(gemm_bf16_dma4_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(D3TH), 0, st, g, tiles_m, tiles_n);
     TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma4");
+    tecm_gemm_kernel = "gemm_bf16_dma4_kernel";
     return 1;
   }
   if (sel && sel[0] == '3') {                           // A/B diagnostics: the four-slot ring geometry
     hipLaunchKernelGGL(gemm_bf16_dma3_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(D3TH), 0, st, g, tiles_m, tiles_n);
     TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma3");
+    tecm_gemm_kernel = "gemm_bf16_dma3_kernel";
     return 1;
   }
   hipLaunchKernelGGL(gemm_bf16_dma_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(DNTH), 0, st, g, tiles_m, tiles_n);
   TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma");
+  tecm_gemm_kernel = "gemm_bf16_dma_kernel";
   return 1;
 }

@@ -945,6 +945,9 @@ int launch(const TecmGemm& g, hipStream_t st) {
   dim3 grid((unsigned)(tiles_m * tiles_n), 1, (unsigned)splits);
   hipLaunchKernelGGL((gemm_bf16_kernel<ALAY, BLAY, WIN, DROP, ADT, BDT>), grid, dim3(NTH), 0, st, g, tiles_m, tiles_n, k_chunk);
   TECM_CHECK_LAUNCH("tecm_gemm_bf16");
+  static const std::string name = "gemm_bf16_kernel<" + std::to_string(ALAY) + "," + std::to_string(BLAY) +
+                                  (WIN ? ",true" : ",false") + (DROP ? ",true>" : ",false>");   // ADT / BDT are not part of the name
+  tecm_gemm_kernel = name.c_str();
   return splits;
 }
 

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(tecm_p8::NTH, 1) void gemm_bf16_p8_kernel(const Tec
 // blocks are re-issued as CUs free up and the last, partly filled round runs faster per tile -- the launch is bound by what
 // the CUs share, not by the slowest CU -- so wider results (N = 800 / 2304: +2 %; N = 3072: +9 %) and 192-row tiles
 // (+0 .. +13 %) stay on 256 rows; with a residual + dropout epilogue the two heights tie.
-// TECM_P8_ROWS = 128 | 112 | 96 pins it (A/B diagnostics).  Mirrored by tecmollm/ops.py (kernel names of the roofline).
+// TECM_P8_ROWS = 128 | 112 | 96 pins it (A/B diagnostics).
 extern "C" int tecm_p8_rows(int64_t M, int64_t N) {
   if (const char* e = std::getenv("TECM_P8_ROWS")) {     // read per call: the tests pin one height after another
     const int v = atoi(e);
@@ -200,9 +200,16 @@ int tecm_gemm16_p8_try(const TecmGemm& g, hipStream_t st) {
   const int wr = tecm_p8_rows(g.M, g.N);
   const int tiles_m = (int)((g.M + 2 * wr - 1) / (2 * wr));
   const dim3 grid((unsigned)(tiles_m * tiles_n)), block(tecm_p8::NTH);
-  if (wr == 128) hipLaunchKernelGGL(gemm_bf16_p8_kernel<128>, grid, block, 0, st, g, tiles_m, tiles_n);
-  else if (wr == 112) hipLaunchKernelGGL(gemm_bf16_p8_kernel<112>, grid, block, 0, st, g, tiles_m, tiles_n);
-  else hipLaunchKernelGGL(gemm_bf16_p8_kernel<96>, grid, block, 0, st, g, tiles_m, tiles_n);
+  if (wr == 128) {
+    hipLaunchKernelGGL(gemm_bf16_p8_kernel<128>, grid, block, 0, st, g, tiles_m, tiles_n);
+    tecm_gemm_kernel = "gemm_bf16_p8_kernel<128>";
+  } else if (wr == 112) {
+    hipLaunchKernelGGL(gemm_bf16_p8_kernel<112>, grid, block, 0, st, g, tiles_m, tiles_n);
+    tecm_gemm_kernel = "gemm_bf16_p8_kernel<112>";
+  } else {
+    hipLaunchKernelGGL(gemm_bf16_p8_kernel<96>, grid, block, 0, st, g, tiles_m, tiles_n);
+    tecm_gemm_kernel = "gemm_bf16_p8_kernel<96>";
+  }
   TECM_CHECK_LAUNCH("tecm_gemm_bf16/p8");
   return 1;
 }

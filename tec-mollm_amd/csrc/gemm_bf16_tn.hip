@@ -285,6 +285,7 @@ static int tn_launch(const TecmGemm& g, int splits, hipStream_t st) {
   else
     hipLaunchKernelGGL((gemm_bf16_tn_kernel<WR, WC, FM, FN, false>), dim3(grid), dim3(256), 0, st, a);
   TECM_CHECK_LAUNCH("tecm_gemm_bf16/tn");
+  tecm_gemm_kernel = "gemm_bf16_tn_kernel";
   return splits;
 }
 

@@ -30,6 +30,7 @@
 #ifndef TECM_BIG_THREADS
 #define TECM_BIG_THREADS 512
 #endif
+#include <string>
 #include <utility>
 #ifndef TECM_ABLATE
 #define TECM_ABLATE 0      // experiments only: 1 no staging, 2 no LDS reads either, 3 loads only, 4 stores only
@@ -1046,6 +1047,10 @@ int launch(const TecmGemm& g, hipStream_t st) {
   hipLaunchKernelGGL((gemm_kernel<ALAY, BLAY, AVEC, BVEC, BN, WIN, DROP, BMT>), grid, dim3(threads_for(BN)), 0, st, g, tiles_m,
                      tiles_n, k_chunk);
   TECM_CHECK_LAUNCH("tecm_gemm_f32");
+  static const std::string name = "gemm_kernel<" + std::to_string(ALAY) + "," + std::to_string(BLAY) + "," + std::to_string(AVEC) +
+                                  "," + std::to_string(BVEC) + "," + std::to_string(BN) + (WIN ? ",true" : ",false") +
+                                  (DROP ? ",true," : ",false,") + std::to_string(BMT) + ">";
+  tecm_gemm_kernel = name.c_str();
   return splits;      // > 0: number of K splits actually launched
 }
 

@@ -342,6 +342,8 @@ int launch_split(const TecmGemm& g, hipStream_t st) {
   dim3 grid((unsigned)(tiles_m * tiles_n), 1, (unsigned)splits);
   hipLaunchKernelGGL((gemm_x3_kernel<NS, BK>), grid, dim3(NTH), 0, st, g, tiles_m, tiles_n, k_chunk);
   TECM_CHECK_LAUNCH("tecm_gemm_bf16x3/x6");
+  static const std::string name = "gemm_x3_kernel<" + std::to_string(NS) + "," + std::to_string(BK) + ">";
+  tecm_gemm_kernel = name.c_str();
   return splits;
 }
 

@@ -1285,6 +1285,12 @@ int gn_blocks(int64_t S) {
 
 }  // namespace
 
+// 1 when BOTH directions have a register-resident kernel that takes bf16 act / dy (4 or 8 waves per sequence, at most 9 quads
+// per lane; the 2-wave geometry is forward only), else 0
+extern "C" int tecm_gn_reg_supported(int32_t L, int32_t N, int32_t Cout) {
+  return gn_reg_pairs(L, N, Cout, 4, 9, nullptr, nullptr) > 0 || gn_reg_pairs(L, N, Cout, 8, 9, nullptr, nullptr) > 0 ? 1 : 0;
+}
+
 // 1 when the all-bf16 GroupNorm kernels (TECM_GN_Y_BF16) serve sequences of L steps x 3*Cout channels, else 0
 extern "C" int tecm_gn_y16_supported(int32_t L, int32_t N, int32_t Cout) { return gn16_ng(L, N, Cout, nullptr, nullptr) > 0 ? 1 : 0; }
 

@@ -895,6 +895,23 @@ extern "C" int tecm_spatial_bwd_blocks(const TecmSpatial* dp) {
   return (int)bwd_blocks(*dp);
 }
 
+// Dynamic LDS of spatial_bwd_kernel: the map, or the final reduction's block behind it where the data arrays are too small
+static size_t bwd_lds(const TecmSpatial& d) {
+  const Map m = make_map(d);
+  size_t floats = (size_t)m.total;
+  if (floats < (size_t)red_offset(m) + RED_FLOATS) floats = (size_t)red_offset(m) + RED_FLOATS;
+  return sizeof(float) * floats;
+}
+
+extern "C" int64_t tecm_spatial_bwd_lds_bytes(int32_t win_max, int32_t tile_nodes, int32_t tile_edges_max, int32_t Demb) {
+  TecmSpatial d = {};
+  d.win_max = win_max;
+  d.tile_nodes = tile_nodes;
+  d.tile_edges_max = tile_edges_max;
+  d.Demb = Demb;
+  return (int64_t)bwd_lds(d);
+}
+
 extern "C" int tecm_spatial_bwd(const TecmSpatial* dp, const TecmSpatialGrads* gp, void* stream) {
   TECM_REQUIRE(dp != nullptr && gp != nullptr, TECM_E_ARG, "tecm_spatial_bwd: null descriptor");
   const TecmSpatial& d = *dp;
@@ -922,10 +939,7 @@ extern "C" int tecm_spatial_bwd(const TecmSpatial* dp, const TecmSpatialGrads* g
   TECM_REQUIRE(d.win_max <= SRC_R_MAX * 256, TECM_E_LDS,
                "tecm_spatial_bwd: neighbour window of %d rows exceeds %d; renumber the graph (e.g. RCM) or shrink tile_nodes",
                d.win_max, SRC_R_MAX * 256);
-  const Map m = make_map(d);
-  size_t floats = (size_t)m.total;
-  if (floats < (size_t)red_offset(m) + RED_FLOATS) floats = (size_t)red_offset(m) + RED_FLOATS;
-  const size_t lds = sizeof(float) * floats;
+  const size_t lds = bwd_lds(d);
   TECM_REQUIRE(lds <= (size_t)kLdsBudget, TECM_E_LDS,
                "tecm_spatial_bwd: neighbour window of %d rows needs %zu B of LDS (> 160 KiB); renumber the graph "
                "(e.g. RCM) or shrink tile_nodes", d.win_max, lds);

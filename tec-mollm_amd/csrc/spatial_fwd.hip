@@ -557,6 +557,14 @@ size_t tecm_spatial_fwd_lds(const TecmSpatial& d) {
                           d.tile_nodes + 1 + d.tile_edges_max + SCR_FLOATS);
 }
 
+extern "C" int64_t tecm_spatial_fwd_lds_bytes(int32_t win_max, int32_t tile_nodes, int32_t tile_edges_max) {
+  TecmSpatial d = {};
+  d.win_max = win_max;
+  d.tile_nodes = tile_nodes;
+  d.tile_edges_max = tile_edges_max;
+  return (int64_t)tecm_spatial_fwd_lds(d);
+}
+
 extern "C" int tecm_spatial_fwd(const TecmSpatial* dp, void* stream) {
   TECM_REQUIRE(dp != nullptr, TECM_E_ARG, "tecm_spatial_fwd: null descriptor");
   const TecmSpatial& d = *dp;

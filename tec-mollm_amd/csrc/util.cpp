@@ -12,4 +12,7 @@ void tecm_set_error(const char* fmt, ...) {
 }
 
 extern "C" const char* tecm_last_error(void) { return g_err; }
+
+thread_local const char* tecm_gemm_kernel = "";
+extern "C" const char* tecm_gemm_last_kernel(void) { return tecm_gemm_kernel; }
 extern "C" int tecm_abi_version(void) { return TECM_ABI_VERSION; }

@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TECM_LIB", os.path.join(_HERE, "libtecmollm_hip.so"))   # override for experiments
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 c_f32p = C.c_void_p
 
@@ -166,6 +166,9 @@ EXPORTS = {
     "tecm_gemm_bf16": (C.c_int, [C.POINTER(TecmGemm), C.c_void_p]),
     "tecm_gemm_bf16x3": (C.c_int, [C.POINTER(TecmGemm), C.c_void_p]),
     "tecm_gemm_bf16x6": (C.c_int, [C.POINTER(TecmGemm), C.c_void_p]),
+    "tecm_gemm_last_kernel": (C.c_char_p, []),
+    "tecm_spatial_fwd_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "tecm_spatial_bwd_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "tecm_spatial_fwd": (C.c_int, [C.POINTER(TecmSpatial), C.c_void_p]),
     "tecm_spatial_fwd2_ws_floats": (C.c_int64, [C.POINTER(TecmSpatial)]),
     "tecm_spatial_fwd2": (C.c_int, [C.POINTER(TecmSpatial), c_f32p, C.c_void_p]),
@@ -176,6 +179,7 @@ EXPORTS = {
     "tecm_groupnorm_gelu_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
     "tecm_gn_y16_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "tecm_gn_reg_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "tecm_groupnorm_gelu_bwd": (C.c_int, [c_f32p, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                           C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, c_f32p, C.c_void_p]),
@@ -210,11 +214,13 @@ EXPORTS = {
     "tecm_conv_fwd_pack_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "tecm_conv_fwd_f32": (C.c_int, [C.POINTER(TecmConvFwd), C.c_void_p]),
     "tecm_conv_dw_workspace": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
+    "tecm_conv_dw_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "tecm_conv_dw_bf16": (C.c_int, [C.POINTER(TecmConvDw), C.c_void_p]),
     "tecm_conv_dw_f32": (C.c_int, [C.POINTER(TecmConvDw), C.c_void_p]),
     "tecm_conv_dx_pack_f32": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "tecm_conv_dx_f32": (C.c_int, [C.POINTER(TecmConvDx), C.c_void_p]),
     "tecm_conv_fwd_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tecm_conv_fwd_stats_supported": (C.c_int, [C.c_int32]),
     "tecm_gemm_tn_splits": (C.c_int32, [C.c_int64, C.c_int64, C.c_int64]),
     "tecm_p8_rows": (C.c_int, [C.c_int64, C.c_int64]),
     "tecm_conv_dx_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

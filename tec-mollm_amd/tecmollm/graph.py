@@ -15,8 +15,9 @@ from typing import Dict, Tuple
 import numpy as np
 import torch
 
+from ._lib import lib
+
 LDS_BYTES = 160 * 1024
-C_FEAT = 22
 
 
 @dataclass
@@ -63,9 +64,6 @@ def tile_windows(rowptr: np.ndarray, colidx: np.ndarray, num_nodes: int, tile_no
     return lo, hi
 
 
-CP = 24
-
-
 def by_source_lists(rowptr: np.ndarray, colidx: np.ndarray, num_nodes: int, tile_nodes: int, lo: np.ndarray,
                     hi: np.ndarray):
     """Per tile, the tile's by-target edge segment regrouped by SOURCE (the backward gathers d x_l per source
@@ -93,30 +91,17 @@ def by_source_lists(rowptr: np.ndarray, colidx: np.ndarray, num_nodes: int, tile
     return np.concatenate(ptrs), src_col, np.asarray(offs, dtype=np.int32)
 
 
-MAXI = 40           # items a persistent block may own (csrc/spatial_fwd.hip, spatial_bwd.hip)
-SCR_FWD, SCR_BWD = 1192, 2888
-RED_FLOATS = 8 * 8 * 4 * 64
 MAX_WINDOW = 512    # the backward's by-source pass: two rounds of 256 rows
 
 
-def _r4(n: int) -> int:
-    return (n + 3) & ~3
-
-
 def lds_bytes_fwd(win: int, tile_nodes: int, tile_edges: int = 0) -> int:
-    """Dynamic LDS of spatial_fwd_kernel (must match csrc/spatial_fwd.hip:tecm_spatial_fwd_lds): two item slots."""
-    P, wm4 = win | 1, _r4(win)
-    return 4 * (2 * (_r4(C_FEAT * P) + wm4 * CP + tile_nodes * CP) + MAXI * 96 + tile_nodes + 1 + tile_edges + SCR_FWD)
+    """Dynamic LDS of spatial_fwd_kernel, asked of the library (the launcher refuses with the same number)."""
+    return lib().tecm_spatial_fwd_lds_bytes(win, tile_nodes, tile_edges)
 
 
 def lds_bytes_bwd(win: int, tile_nodes: int, demb: int = 16, tile_edges: int = 0) -> int:
-    """Dynamic LDS of spatial_bwd_kernel (must match csrc/spatial_bwd.hip:make_map / red_offset)."""
-    P, wm4 = win | 1, _r4(win)
-    T, E = tile_nodes, tile_edges
-    scr = (_r4((C_FEAT + 1) * P) + wm4 * CP + 4 * T * CP + (E + T) * 4 + _r4(demb * P) + MAXI * 32 + MAXI * 4)
-    total = scr + SCR_BWD + (T + 1) + E + (wm4 + 1) + E
-    red = 0 if scr >= RED_FLOATS else total
-    return 4 * max(total, red + RED_FLOATS)
+    """Dynamic LDS of spatial_bwd_kernel, asked of the library (the launcher refuses with the same number)."""
+    return lib().tecm_spatial_bwd_lds_bytes(win, tile_nodes, tile_edges, demb)
 
 
 def build(edge_index: torch.Tensor, num_nodes: int, device: torch.device, demb: int = 16) -> GraphMeta:

@@ -66,8 +66,8 @@ def gemm(M: int, N: int, K: int, A: torch.Tensor, lda: int, B: torch.Tensor, ldb
     3 bf16x6 (three-way split, fp32-grade).
     bf16=True asks for the bf16 matrix cores (operands rounded to bf16, fp32 accumulate); calls the bf16
     kernel cannot serve (N < 64 output columns or operands that are not 16-byte friendly) run on the exact
-    fp32 kernel instead -- the choice is a pure function of shapes/alignment (`uses_bf16`), never silent
-    with respect to the tests, which mirror it."""
+    fp32 kernel instead -- the choice is a pure function of shapes/alignment (`uses_bf16`), never silent:
+    with timing on, every record carries the name of the kernel the library launched (tecm_gemm_last_kernel)."""
     g = TecmGemm()
     g.M, g.N, g.K = M, N, K
     io = (IO_A_BF16 if A.dtype == torch.bfloat16 else 0) | (IO_B_BF16 if B.dtype == torch.bfloat16 else 0) | \
@@ -122,7 +122,7 @@ def gemm(M: int, N: int, K: int, A: torch.Tensor, lda: int, B: torch.Tensor, ldb
     e0.record()
     check(fn(C.byref(g), stream_ptr()), what)
     e1.record()
-    name = ("gemm_x3_kernel<3,16>" if mode == PREC_BF16X6 else "gemm_x3_kernel<2,32>") if use3 else _kernel_name(g, use16)
+    name = lib().tecm_gemm_last_kernel().decode()
     if _timing_detail:
         name += (f" M={M} N={N} K={K} win={g.a_win.enabled}{g.b_win.enabled}{g.c_win.enabled}"
                  f" drop={int(g.a_drop.p > 0)}{int(g.b_drop.p > 0)}{int(g.out_drop.p > 0)} split={g.split_k}"
@@ -180,98 +180,6 @@ def _bf16_ok(g: TecmGemm) -> bool:
 # ------------------------------------------------------------------ per-launch timing (bench.py roofline)
 _timing = None
 _timing_detail = False
-
-
-def _vec(p: int, ld: int, w: TecmWin, inner_is_k: bool, K: int) -> int:
-    v = 4
-    while v > 1:
-        ok = p % (4 * v) == 0 and ld % v == 0
-        if w.enabled:
-            ok = ok and w.Cw % v == 0
-        if inner_is_k:
-            ok = ok and K % v == 0
-        if ok:
-            break
-        v >>= 1
-    return v
-
-
-def _kernel_name(g: TecmGemm, use16: bool = False) -> str:
-    """Name of the template instance csrc/gemm.hip dispatches to (mirrors pick_vec / dispatch_vec)."""
-    if use16:
-        win16 = "true" if (g.a_win.enabled or g.b_win.enabled) else "false"
-        drp16 = "true" if (g.a_drop.p > 0 or g.b_drop.p > 0) else "false"
-        if (g.io_bf16 & (IO_A_BF16 | IO_B_BF16)) and not (g.a_layout == A_MK and g.b_layout == B_NK and win16 == "false"):
-            win16 = "true"                             # the bf16-resident window / transposed instances are built WIN = true
-        both16 = (g.io_bf16 & IO_A_BF16) and (g.io_bf16 & IO_B_BF16)
-        # the straight-line epilogues (gemm_impl.h epi_fast_mode >= 0; mirrors tecm_gemm16_dma_try's fast_epi)
-        streams = (1 if g.residual else 0) + (1 if g.dact_src else 0) + (1 if g.accumulate else 0)
-        if g.c_win.enabled:
-            fast_epi = streams == 0 and not g.rowbias and not g.preact and not (g.io_bf16 & (IO_C_BF16 | IO_PRE_BF16))
-        else:
-            fast_epi = streams == 0 if g.rowbias else streams <= 1
-        p8 = os.environ.get("TECM_BF16_P8", "")[:1]                            # mirrors tecm_gemm16_p8_try (gemm_bf16_p8.hip)
-
-        def p8_takes(a_rows: int) -> bool:
-            return (fast_epi and not os.environ.get("TECM_BF16_DMA", "") and p8 != "0" and g.K >= 128 and g.K % 32 == 0
-                    and g.M >= 256 and g.N >= 128 and (p8 == "1" or g.N >= 768 or not 1 <= g.N % 256 <= 128)
-                    and (a_rows * g.lda + 64) * 2 < 2 ** 32 and (g.N * g.ldb + 64) * 2 < 2 ** 32)
-        if (both16 and g.a_layout == A_MK and g.b_layout == B_NK and g.a_win.enabled and not g.b_win.enabled and drp16 == "false"
-                and g.a_win.pad == 0 and g.a_win.Cw % 64 == 0 and g.split_k <= 1 and g.M >= 256 and g.N >= 128
-                and os.environ.get("TECM_BF16_DMA", "")[:1] != "0"):
-            w = g.a_win                                    # the window route of tecm_gemm16_dma_try
-            if ((w.Lout - 1) * w.stride_t + w.taps <= w.Lin and g.M % (w.Lout * w.N) == 0
-                    and p8_takes(g.M // (w.Lout * w.N) * w.Lin * w.N)):
-                return f"gemm_bf16_p8_kernel<{lib().tecm_p8_rows(g.M, g.N)}>"
-            return "gemm_bf16_dma_kernel"
-        # mirrors tecm_gemm16_dma_try (csrc/gemm_bf16_dma.hip); the float4-epilogue condition holds for every bf16 call
-        sel = os.environ.get("TECM_BF16_DMA", "")[:1]
-        if (both16 and g.a_layout == A_MK and g.b_layout == B_NK and not g.a_win.enabled and not g.b_win.enabled
-                and g.split_k <= 1 and g.N % 4 == 0 and g.K % 32 == 0 and g.K >= 32 and g.M >= 256
-                and (g.N >= 128 or g.N == 32) and sel != "0"):
-            k32, n_small = g.K < 64, g.N < 128
-            can16 = not g.c_win.enabled and not g.rowbias and streams <= 1
-            if p8_takes(g.M):
-                return f"gemm_bf16_p8_kernel<{lib().tecm_p8_rows(g.M, g.N)}>"
-            narrow = n_small or (sel == "2" if (sel and not k32) else 1 <= g.N % 256 <= 128)   # the 256 x 128 geometry (N = 800)
-            if narrow:
-                return "gemm_bf16_dma2_kernel"
-            ring = sel == "4"                                                 # the four-slot ring, anti-phase wave groups (A/B)
-            can16 = not g.c_win.enabled and not g.rowbias and \
-                (1 if g.residual else 0) + (1 if g.dact_src else 0) + (1 if g.accumulate else 0) <= 1
-            if can16 and sel in ("6", "7"):                                   # four-wave blocks, two per CU (A/B)
-                return "gemm_bf16_dma6_kernel<256,128,2,2>" if sel == "6" else "gemm_bf16_dma6_kernel<128,256,1,4>"
-            want16 = sel in ("5", "8") if (sel and not k32) else True          # the ring with 16x16x32 MFMAs
-            if can16 and want16:
-                tn_ = (g.N + 255) // 256
-                cost = lambda bm: ((((g.M + bm - 1) // bm) * tn_ + 255) // 256) * bm     # rounds of blocks on 256 CUs x tile height
-                tall = True if sel == "8" else (False if (sel == "5" or os.environ.get("TECM_BF16_TALL", "")[:1] == "0")
-                                                else cost(288) * 100 < cost(256) * 95)
-                return "gemm_bf16_dma5w_kernel" if tall else "gemm_bf16_dma5_kernel"
-            return "gemm_bf16_dma4_kernel" if ring else ("gemm_bf16_dma3_kernel" if sel == "3" else "gemm_bf16_dma_kernel")
-        # mirrors tecm_gemm16_tn_try (csrc/gemm_bf16_tn.hip): weight gradients from bf16 tensors in their natural orientation
-        if (both16 and g.a_layout == A_KM and g.b_layout == B_KN and g.split_k >= 2 and not g.a_win.enabled
-                and (not g.b_win.enabled or g.b_win.pad == 0) and os.environ.get("TECM_BF16_TN", "")[:1] != "0"
-                and lib().tecm_gemm_tn_splits(g.M, g.N, g.K) > 0):
-            return "gemm_bf16_tn_kernel"
-        return f"gemm_bf16_kernel<{g.a_layout},{g.b_layout},{win16},{drp16}>"
-    av = _vec(g.A, g.lda, g.a_win, g.a_layout == A_MK, g.K)
-    bv = _vec(g.B, g.ldb, g.b_win, g.b_layout == B_NK, g.K)
-    if av == 4 and bv == 4:
-        pair = (4, 4)
-    elif g.a_layout == A_MK:
-        pair = (2, 1) if av >= 2 else (1, 1)
-    else:
-        pair = (4, 2) if (av == 4 and bv >= 2) else (1, 1)
-    bn = 32 if g.N <= 32 else (64 if g.N <= 64 else 128)
-    m64 = ",64" if (g.a_layout == A_KM and g.M <= 64 and bn > 32 and pair == (4, 4)) else ",128"   # block rows
-    if pair == (4, 4):                      # float4 loaders: one instance per (WIN, DROP); narrower vectors: the general one
-        win = bool(g.a_win.enabled or g.b_win.enabled)
-        drp = bool(g.a_drop.p > 0 or g.b_drop.p > 0)
-    else:
-        win = drp = True
-    flags = f",{'true' if win else 'false'},{'true' if drp else 'false'}"
-    return f"gemm_kernel<{g.a_layout},{g.b_layout},{pair[0]},{pair[1]},{bn}{flags}{m64}>"
 
 
 def enable_gemm_timing(detail: bool = False) -> list:
@@ -403,10 +311,7 @@ def gn_reg_ok(L: int, N: int, Cout: int) -> bool:
     at most 9 float4 per lane) serve BOTH directions -- the only kernels that read / write bf16 activations.  Longer
     sequences (the reference's default L_in = 336) take the multi-pass fp32 kernels, and the conv block then keeps its
     activations fp32 in bf16 mode too."""
-    quads = L * (3 * Cout // 4)
-    if L * N * 3 * Cout >= 1 << 31:
-        return False
-    return any(quads % (64 * wps) == 0 and quads // (64 * wps) <= 9 for wps in (4, 8))
+    return lib().tecm_gn_reg_supported(L, N, Cout) == 1
 
 
 def _gn_io(y: torch.Tensor, out: torch.Tensor) -> int:
@@ -669,9 +574,8 @@ conv_dx_bf16 = conv_dx      # round-3 name (tests)
 
 
 def conv_dw_seq_ok(Lc: int, Cout: int, ld_in: int) -> bool:
-    """Shapes the sequence-tile weight-gradient kernel (csrc/conv_dw_seq.hip) serves."""
-    return (Lc % 4 == 0 and Lc > 0 and Cout in (64, 128) and ld_in in (24, 64)
-            and os.environ.get("TECM_CONV_DW_SEQ", "1")[:1] != "0")
+    """Shapes the sequence-tile weight-gradient kernel (csrc/conv_dw_seq.hip) serves (tecm_conv_dw_supported)."""
+    return os.environ.get("TECM_CONV_DW_SEQ", "1")[:1] != "0" and lib().tecm_conv_dw_supported(Lc, Cout, ld_in) == 1
 
 
 _cu_count = {}
@@ -718,8 +622,8 @@ def conv_fwd_seq_ok(Lc: int, Cout: int, ld_in: int, f32: bool = False) -> bool:
 
 
 def conv_fwd_stats_ok(Lc: int) -> bool:
-    """conv_fwd can compute the GroupNorm statistics when one tile holds a whole sequence (csrc/conv_seq.hip: 48 time steps)."""
-    return Lc <= 48 and os.environ.get("TECM_CONV_STATS", "1")[:1] != "0"
+    """conv_fwd can compute the GroupNorm statistics when one tile holds a whole sequence (tecm_conv_fwd_stats_supported)."""
+    return os.environ.get("TECM_CONV_STATS", "1")[:1] != "0" and lib().tecm_conv_fwd_stats_supported(Lc) == 1
 
 
 def conv_fwd(inp: torch.Tensor, w3: torch.Tensor, w5: torch.Tensor, w7: torch.Tensor, bias: torch.Tensor,

@@ -113,6 +113,71 @@ def test_gemm_dropout_prologue_epilogue_match_numpy_mirror(dev):
     assert 0.07 < frac < 0.13
 
 
+# ----------------------------------------------------------------------------- the library names the kernel it launched
+def _launch_named(ops, dev, M, N, K, prec=0, op16=False, km_kn=False, split_k=1, awin=None, drop=False, two_streams=False):
+    """One ops.gemm call on zeros: only the route matters.  awin = (Bq, Lin, Nn, Cw, taps, pad): A is the window view
+    (stride 1, Lout = Lin) of a (Bq, Lin, Nn, Cw) tensor; two_streams: a residual AND an accumulating C."""
+    dt = torch.bfloat16 if op16 else torch.float32
+    z = lambda *shape: torch.zeros(*shape, device=dev, dtype=dt)      # noqa: E731
+    kw = dict(bf16=prec, split_k=split_k)
+    if km_kn:
+        A, lda, B, ldb = z(K, M), M, z(K, N), N
+        kw.update(a_layout=ops.A_KM, b_layout=ops.B_KN)
+    else:
+        A, lda, B, ldb = z(M, K), K, z(N, K), K
+    if awin:
+        Bq, Lin, Nn, Cw, taps, pad = awin
+        assert M == Bq * Lin * Nn and K == taps * Cw
+        A, lda = z(Bq, Lin, Nn, Cw), Cw
+        kw.update(a_win=ops.win(Nn, Lin, Lin, 1, taps, Cw, pad))
+    if drop:
+        kw.update(a_drop=ops.drop(0.1, 12345, K))
+    C = torch.zeros(M, N, device=dev)
+    if two_streams:
+        kw.update(residual=(torch.zeros(M, N, device=dev), N), accumulate=True)
+    ops.gemm(M, N, K, A, lda, B, ldb, C, N, **kw)
+
+
+_NAMED = [  # expected name (a literal: what the dispatcher's former Python mirror said for this call), shape, route
+    ("gemm_kernel<0,0,4,4,32,false,false,128>", (70, 24, 36), {}),
+    ("gemm_kernel<0,0,4,4,64,false,false,128>", (70, 64, 36), {}),
+    ("gemm_kernel<0,0,4,4,128,false,false,128>", (70, 200, 36), {}),
+    ("gemm_kernel<0,0,1,1,64,true,true,128>", (70, 64, 37), {}),                       # K % 2 != 0: the general instance
+    ("gemm_kernel<1,1,4,4,128,false,false,64>", (64, 72, 36), dict(km_kn=True)),      # the 64-row tile
+    ("gemm_kernel<0,0,4,4,64,true,false,128>", (80, 64, 36), dict(awin=(2, 8, 5, 12, 3, 1))),
+    ("gemm_kernel<0,0,4,4,64,false,true,128>", (70, 64, 36), dict(drop=True)),
+    ("gemm_kernel<0,0,4,4,32,false,false,128>", (70, 32, 36), dict(prec=1)),          # bf16 asked, N < 64: the fp32 kernel
+    ("gemm_bf16_kernel<0,0,false,false>", (300, 64, 72), dict(prec=1)),               # fp32 operands: register-staged
+    ("gemm_bf16_dma5_kernel", (300, 256, 64), dict(prec=1, op16=True)),               # bf16 operands: the 16x16x32 ring
+    ("gemm_bf16_dma_kernel", (300, 256, 64), dict(prec=1, op16=True, two_streams=True)),   # ... the two-slot kernel
+    ("gemm_bf16_dma2_kernel", (256, 384, 64), dict(prec=1, op16=True)),               # the 128-column geometry
+    ("gemm_bf16_p8_kernel<112>", (257, 768, 128), dict(prec=1, op16=True)),           # eight phases, 224-row tiles
+    ("gemm_bf16_tn_kernel", (64, 192, 4096), dict(prec=1, op16=True, km_kn=True, split_k=-1)),   # split_k: the library's
+    ("gemm_x3_kernel<2,32>", (70, 64, 36), dict(prec=2)),
+    ("gemm_x3_kernel<3,16>", (70, 64, 36), dict(prec=3)),
+]
+
+
+@pytest.mark.parametrize("want,shape,route", _NAMED, ids=[f"{i}-{c[0].split('<')[0]}" for i, c in enumerate(_NAMED)])
+def test_gemm_reports_the_kernel_it_launched(dev, want, shape, route, monkeypatch):
+    """tecm_gemm_last_kernel, as ops.gemm records it with timing on: one tiny call per launcher family, the smallest shapes
+    that reach each branch, with every A/B switch of the dispatchers unset."""
+    from tecmollm import ops, _lib
+    for var in ("TECM_BF16_DMA", "TECM_BF16_P8", "TECM_BF16_TN", "TECM_BF16_TALL", "TECM_P8_ROWS"):
+        monkeypatch.delenv(var, raising=False)
+    route = dict(route)
+    if route.get("split_k") == -1:
+        route["split_k"] = _lib.lib().tecm_gemm_tn_splits(*shape)
+        assert route["split_k"] >= 2
+    rec = ops.enable_gemm_timing()
+    try:
+        _launch_named(ops, dev, *shape, **route)
+        names = list(ops.summarize_gemm_timing(rec))
+    finally:
+        ops.disable_gemm_timing()
+    assert names == [want]
+
+
 # ----------------------------------------------------------------------------- GEMM, window views
 def _tm(x_scl):
     """(S, C, L) reference conv layout -> time-major (B=S, L, N=1, C)."""
@@ -616,9 +681,9 @@ def test_attention_fwd_kv_reproducible(dev, T, q16, p):
 
 
 @pytest.mark.parametrize("L,Cout", [(48, 64), (24, 128), (96, 64), (336, 64), (168, 128), (100, 64), (12, 256)])
-def test_gn_reg_ok_mirrors_the_library(dev, L, Cout):
-    """ops.gn_reg_ok (what decides whether a conv block keeps bf16 activations) against the library itself: bf16 act / dy
-    are accepted exactly where it says so, and refused loudly elsewhere."""
+def test_gn_kernels_accept_bf16_tensors_exactly_where_tecm_gn_reg_supported_says(dev, L, Cout):
+    """ops.gn_reg_ok = tecm_gn_reg_supported (what decides whether a conv block keeps bf16 activations) against the launchers
+    of the same library: bf16 act / dy are accepted exactly where the query says so, and refused loudly elsewhere."""
     from tecmollm import ops
     Bn, N, CT = 1, 3, 3 * Cout
     y = _rand(Bn, L, N, CT, dev=dev, seed=1)

@@ -66,6 +66,30 @@ def test_conv_sequence_kernels_report_what_they_serve_including_the_lds_budget(b
     assert not ops.conv_fwd_seq_ok(48, 256, 64) and not ops.conv_dx_seq_ok(20, 64, 24) and not ops.conv_dx_seq_ok(48, 64, 128)
 
 
+def test_spatial_lds_bytes_and_routing_queries_are_pinned(built_lib):
+    """The host queries that replaced hand-kept Python copies of C++ decisions, against literal values of those copies as they
+    stood when they were deleted (graph.lds_bytes_fwd / lds_bytes_bwd, ops.gn_reg_ok), and the tiling graph.build derives
+    from them for the 2911-node grid.  Pure host arithmetic: no GPU call."""
+    from tecmollm import _lib, graph
+    h = _lib.lib()
+    for (win_max, tile_nodes, tile_edges_max, demb), fwd, bwd in (
+            ((256, 112, 1110, 16), 140924, 154904),                # the 2911-node grid
+            ((1, 1, 0, 0), 21288, 83756),
+            ((3, 2, 4, 16), 21852, 84640),
+            ((512, 128, 1280, 16), 238948, 230984),                # over the 160 KiB budget in both directions
+            ((330, 128, 1280, 0), 172356, 163416)):
+        assert h.tecm_spatial_fwd_lds_bytes(win_max, tile_nodes, tile_edges_max) == fwd
+        assert h.tecm_spatial_bwd_lds_bytes(win_max, tile_nodes, tile_edges_max, demb) == bwd
+        assert graph.lds_bytes_fwd(win_max, tile_nodes, tile_edges_max) == fwd
+        assert graph.lds_bytes_bwd(win_max, tile_nodes, demb, tile_edges_max) == bwd
+    for L, Cout in ((48, 64), (24, 128), (96, 64), (12, 256)):
+        assert h.tecm_gn_reg_supported(L, 3, Cout) == 1
+    for L, Cout in ((336, 64), (168, 128), (100, 64)):
+        assert h.tecm_gn_reg_supported(L, 3, Cout) == 0
+    meta = graph.build(R.grid_graph()[0], 2911, torch.device("cpu"))
+    assert (meta.tile_nodes, meta.num_tiles, meta.win_max, meta.tile_edges_max) == (112, 26, 256, 1110)
+
+
 def test_eight_phase_gemm_tile_height_is_chosen_by_tile_count(built_lib, monkeypatch):
     """tecm_p8_rows is pure host arithmetic (no launch; without a GPU it assumes 256 CUs): 224-row tiles only for results at
     most three tiles wide or at most 32 768 rows tall whose tile count then fills the last round of CUs better, 256 rows
@@ -162,7 +186,7 @@ def test_pretrained_gpt2_copy_is_complete_or_raises():
         assert float(full.trunk.wpe.weight.abs().max()) > 0.2     # the real checkpoint (config init is N(0, 0.02))
 
 
-def test_graph_csr_and_windows():
+def test_graph_csr_and_windows(built_lib):
     from tecmollm import graph
     ei, _ = R.grid_graph()
     rowptr, col = graph.csr_by_target(ei.numpy(), 2911)
@@ -180,7 +204,7 @@ def test_graph_csr_and_windows():
     assert graph.lds_bytes_bwd(meta.win_max, meta.tile_nodes) <= 160 * 1024
 
 
-def test_graph_self_loops_dropped_duplicates_kept_and_bad_ids_rejected():
+def test_graph_self_loops_dropped_duplicates_kept_and_bad_ids_rejected(built_lib):
     from tecmollm import graph
     ei = np.array([[0, 1, 1, 2, 2, 3], [1, 1, 0, 1, 1, 9]])
     with pytest.raises(ValueError):

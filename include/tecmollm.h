@@ -33,7 +33,7 @@ extern "C" {
 #define TECM_E_LAUNCH (-3)     /* hipGetLastError() != hipSuccess after the launch       */
 #define TECM_E_LDS (-4)        /* problem does not fit the 160 KiB LDS budget            */
 
-#define TECM_ABI_VERSION 19
+#define TECM_ABI_VERSION 20
 int tecm_abi_version(void);
 /* Human-readable text for the last error on this thread (host pointer, never NULL). */
 const char* tecm_last_error(void);
@@ -278,6 +278,8 @@ int tecm_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const fl
                        int32_t y16d_seq_T, int32_t y16d_seq_N /* both > 0: y16d is written SEQUENCE-major -- the time-major
                                      row (b, t, n) of M = B*T*N goes to row (b, n, t): PredictionHead's view(batch, -1)
                                      (modules.py:307) of ln_f's output as a plain [B*N][T*D] matrix.  0, 0: same rows as y */,
+                       int32_t y16d_f32 /* != 0: y16d is an fp32 matrix (16-byte aligned), dropout(y, drop) unrounded: the
+                                     fp32 head operand -- the values tecm_dropout_apply makes of y, bit for bit */,
                        float* stats /* (M,2) mean,rstd */, int64_t M, int32_t D, float eps, void* stream);
 /* dx = dres (optional) + LN'(dy).  Optional second output dx_masked = dropout(dx, mask_drop): the
  * residual-stream gradient is consumed twice in GPT2Block's backward, once as is (residual path) and
@@ -295,7 +297,7 @@ typedef struct TecmLnAdd {
   int32_t bf16, _pad;
   TecmDrop drop;
 } TecmLnAdd;
-/* dy in the sequence-major form tecm_layernorm_fwd can write y16d in (rows (b, n, t), bf16) and still in front of the
+/* dy in the sequence-major form tecm_layernorm_fwd can write y16d in (rows (b, n, t), bf16 or fp32) and still in front of the
  * forward's dropout:  dy[(b,t,n)][c] = keep((b,t,n), c) / (1 - p) * dy16[(b,n,t)][c]  -- the gradient the head's first Linear
  * returns for F.dropout(ln_f(h)) (tec_mollm.py:115), taken as it is.  T == 0 / NULL: plain rows. */
 typedef struct TecmLnDyMap {
@@ -308,7 +310,10 @@ int tecm_layernorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t ld
                        const TecmLnAdd* add /* NULL: none */,
                        int32_t dy_bf16 /* != 0: dy is bf16 -- the gradient a bf16 Linear returns for its input under
                                           autocast (train.py:68) */,
-                       const TecmLnDyMap* dymap /* NULL: none; needs dy_bf16 and no second stream */, void* stream);
+                       const TecmLnDyMap* dymap /* NULL: none; dy bf16 or fp32, no second stream */,
+                       int32_t skip_dx /* != 0: the unmasked dx has no reader -- its store is left out and the dx buffer is not
+                                          touched (still non-NULL: NULL queries); needs dx_masked */,
+                       void* stream);
 
 /* Causal multi-head self-attention over T tokens per sequence (GPT2Attention, modeling_gpt2.py:54-73,
  * :144-226; all-ones attention_mask tec_mollm.py:111 => pure causal).  qkv: (B,T,N,3*D) time-major
@@ -340,6 +345,13 @@ int tecm_colsum(const float* in, int64_t ld, int64_t outer, int64_t inner, int32
 int tecm_colsum_twin(const float* in, int64_t ld, int64_t outer, int64_t inner, int32_t nseg, int32_t C,
                      float* out, int64_t ldo, int32_t accumulate, float scale, const TecmDrop* in_drop,
                      float* workspace, void* twin_bf16, int64_t ld_twin, void* stream);
+
+/* nbuf matrices in[i] of the same (rows, C) shape and leading dimension ld, out[i] (C floats) = their column sums: per
+ * matrix the result of tecm_colsum(in[i], ld, rows, 1, 1, C, out[i], C, 0, 1, NULL, ...) bit for bit (same blocks, same order
+ * of every sum), from one pair of launches for all of them when C > 1024 or rows are not 16-byte friendly (the LayerNorm
+ * backwards' (num_blocks, 2*D) partials, D = 768), else matrix by matrix.  in / out: HOST arrays of device pointers. */
+int tecm_colsum_batch(const float* const* in, float* const* out, int32_t nbuf, int64_t ld, int64_t rows, int32_t C,
+                      float* workspace /* >= max(1024, 256*nbuf) * C floats */, void* stream);
 
 /* nn.HuberLoss(delta) mean (train.py:372) fused with its gradient: pred/target/dpred are (n) floats
  * addressed through pred_index: element e of pred = pred[e], target likewise (both contiguous in the

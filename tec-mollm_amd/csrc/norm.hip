@@ -37,7 +37,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
                                                             int64_t ldy, void* __restrict__ y16, int64_t ldy16,
                                                             void* __restrict__ y16d, int64_t ldy16d, DropCtxN dd,
                                                             float* __restrict__ stats, int64_t M, int D, float eps,
-                                                            int permT, int permN) {
+                                                            int permT, int permN, int yd_f32) {
   seed_now(dd);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t row = (int64_t)blockIdx.x * 4 + wave;
@@ -87,13 +87,16 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float* __restr
       if (y16) tecm_store_bf16x4(static_cast<__bf16*>(y16) + row * ldy16 + c, o.x, o.y, o.z, o.w);
       // ... and bf16(dropout(o)): the LoRA branch's input (peft lora_dropout in front of lora_A, modules.py:181), the
       // cast autocast applies to the DROPPED fp32 value; read by the LoRA-A GEMM and by its weight gradient
+      // (yd_f32: the same output left in fp32 -- fp32 mode's head operand, dropout(ln_f(h)) sequence-major: what
+      //  tecm_dropout_apply would make of y, without y or that pass)
       if (y16d) {
         const uint64_t di = (uint64_t)(row * dd.ld + c);
-        tecm_store_bf16x4(static_cast<__bf16*>(y16d) + drow * ldy16d + c,
-                          o.x * tecm_drop_mult(dd.seed, di, dd.thresh, dd.inv),
-                          o.y * tecm_drop_mult(dd.seed, di + 1, dd.thresh, dd.inv),
-                          o.z * tecm_drop_mult(dd.seed, di + 2, dd.thresh, dd.inv),
-                          o.w * tecm_drop_mult(dd.seed, di + 3, dd.thresh, dd.inv));
+        const float m0 = o.x * tecm_drop_mult(dd.seed, di, dd.thresh, dd.inv);
+        const float m1 = o.y * tecm_drop_mult(dd.seed, di + 1, dd.thresh, dd.inv);
+        const float m2 = o.z * tecm_drop_mult(dd.seed, di + 2, dd.thresh, dd.inv);
+        const float m3 = o.w * tecm_drop_mult(dd.seed, di + 3, dd.thresh, dd.inv);
+        if (yd_f32) *reinterpret_cast<float4*>(static_cast<float*>(y16d) + drow * ldy16d + c) = make_float4(m0, m1, m2, m3);
+        else tecm_store_bf16x4(static_cast<__bf16*>(y16d) + drow * ldy16d + c, m0, m1, m2, m3);
       }
     }
   }
@@ -117,8 +120,8 @@ struct LnAdd {
 };
 
 // DY16: dy is a bf16 matrix (bf16 mode: the gradient a bf16 Linear hands back for its input, train.py:68)
-// DYMAP (with DY16): that matrix is SEQUENCE-major -- row (b, n, t) for the time-major row (b, t, n) this kernel walks -- and
-// still in front of a dropout: dy[row][c] = keep(row, c) / (1 - p) * dy16[(b, n, t)][c].  The gradient the head's first
+// DYMAP (dy bf16 or fp32): that matrix is SEQUENCE-major -- row (b, n, t) for the time-major row (b, t, n) this kernel walks --
+// and still in front of a dropout: dy[row][c] = keep(row, c) / (1 - p) * dy[(b, n, t)][c].  The gradient the head's first
 // Linear returns for F.dropout(hidden) (tec_mollm.py:115, modules.py:307), consumed by ln_f's backward without a pass of
 // its own for the mask or the layout.
 struct LnDyMap {
@@ -168,17 +171,17 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
         if constexpr (DY16) {
           const tecm_bf16x4 h = *reinterpret_cast<const tecm_bf16x4*>(reinterpret_cast<const __bf16*>(dy) + yrow * lddy + c);
           d = make_float4((float)h[0], (float)h[1], (float)h[2], (float)h[3]);
-          if constexpr (DYMAP) {
-            if (dm.drop.thresh) {
-              const uint64_t di = (uint64_t)(row * dm.drop.ld + c);
-              d.x *= tecm_drop_mult(dm.drop.seed, di, dm.drop.thresh, dm.drop.inv);
-              d.y *= tecm_drop_mult(dm.drop.seed, di + 1, dm.drop.thresh, dm.drop.inv);
-              d.z *= tecm_drop_mult(dm.drop.seed, di + 2, dm.drop.thresh, dm.drop.inv);
-              d.w *= tecm_drop_mult(dm.drop.seed, di + 3, dm.drop.thresh, dm.drop.inv);
-            }
-          }
         } else {
-          d = *reinterpret_cast<const float4*>(dy + row * lddy + c);
+          d = *reinterpret_cast<const float4*>(dy + yrow * lddy + c);
+        }
+        if constexpr (DYMAP) {
+          if (dm.drop.thresh) {
+            const uint64_t di = (uint64_t)(row * dm.drop.ld + c);
+            d.x *= tecm_drop_mult(dm.drop.seed, di, dm.drop.thresh, dm.drop.inv);
+            d.y *= tecm_drop_mult(dm.drop.seed, di + 1, dm.drop.thresh, dm.drop.inv);
+            d.z *= tecm_drop_mult(dm.drop.seed, di + 2, dm.drop.thresh, dm.drop.inv);
+            d.w *= tecm_drop_mult(dm.drop.seed, di + 3, dm.drop.thresh, dm.drop.inv);
+          }
         }
         if constexpr (ADD) {
           float4 e;
@@ -220,7 +223,7 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float* __restr
           const float4 r = *reinterpret_cast<const float4*>(dres + row * (int64_t)D + c);
           o[0] += r.x; o[1] += r.y; o[2] += r.z; o[3] += r.w;
         }
-        *reinterpret_cast<float4*>(dx + row * (int64_t)D + c) = make_float4(o[0], o[1], o[2], o[3]);
+        if (dx) *reinterpret_cast<float4*>(dx + row * (int64_t)D + c) = make_float4(o[0], o[1], o[2], o[3]);
         if (dxm) {          // second output: dropout(dx) for the GEMM that consumes the masked gradient
           if (odc.thresh) {
 #pragma unroll
@@ -948,14 +951,14 @@ __global__ __launch_bounds__(384, (NG == 3 ? GN16_OCC : 2)) void gn_gelu_bwd_reg
 
 // ------------------------------------------------------------------------------ column sums
 // stage 1: grid (colblocks, RB, nseg).  Lane = column, the 4 waves stride the block's row chunk.
-__global__ __launch_bounds__(256) void colsum_stage1(const float* __restrict__ in, int64_t ld, int64_t outer,
-                                                     int64_t inner, int nseg, int C, DropCtxN idc,
-                                                     float* __restrict__ ws, int64_t chunk) {
+// (the body is shared with colsum_stage1_batch below: rb / s / RB are the block's row chunk, segment and chunk count)
+__device__ __forceinline__ void colsum_stage1_body(const float* __restrict__ in, int64_t ld, int64_t outer, int64_t inner,
+                                                   int nseg, int C, DropCtxN idc, float* __restrict__ ws, int64_t chunk,
+                                                   int rb, int s, int RB) {
   seed_now(idc);
   __shared__ float red[4][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = blockIdx.x * 64 + lane;
-  const int rb = blockIdx.y, s = blockIdx.z;
   const int64_t total = outer * inner;
   const int64_t beg = (int64_t)rb * chunk;
   const int64_t end = beg + chunk < total ? beg + chunk : total;
@@ -980,7 +983,25 @@ __global__ __launch_bounds__(256) void colsum_stage1(const float* __restrict__ i
   red[wave][lane] = acc;
   __syncthreads();
   if (wave == 0 && c < C)
-    ws[((int64_t)s * gridDim.y + rb) * C + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+    ws[((int64_t)s * RB + rb) * C + c] = (red[0][lane] + red[1][lane]) + (red[2][lane] + red[3][lane]);
+}
+__global__ __launch_bounds__(256) void colsum_stage1(const float* __restrict__ in, int64_t ld, int64_t outer,
+                                                     int64_t inner, int nseg, int C, DropCtxN idc,
+                                                     float* __restrict__ ws, int64_t chunk) {
+  colsum_stage1_body(in, ld, outer, inner, nseg, C, idc, ws, chunk, blockIdx.y, blockIdx.z, gridDim.y);
+}
+// Several matrices of the same (rows, C) shape in ONE launch: blockIdx.z picks the matrix from a pointer table in the
+// kernel arguments; per matrix the blocks, the row chunks and the order of every sum are those of colsum_stage1 /
+// colsum_stage2 on that matrix alone (the LayerNorm backwards' gamma / beta partials: 2 * layers + 1 buffers a step).
+constexpr int COLSUM_BATCH_MAX = 32;
+struct ColsumBatch {
+  const float* in[COLSUM_BATCH_MAX];
+  float* out[COLSUM_BATCH_MAX];
+};
+__global__ __launch_bounds__(256) void colsum_stage1_batch(ColsumBatch tab, int64_t ld, int64_t rows, int C,
+                                                           float* __restrict__ ws, int64_t chunk) {
+  const int z = blockIdx.z, RB = gridDim.y;
+  colsum_stage1_body(tab.in[z], ld, rows, 1, 1, C, DropCtxN{}, ws + (int64_t)z * RB * C, chunk, blockIdx.y, 0, RB);
 }
 
 // stage 1, float4 form for 16-byte friendly inputs: a block owns a chunk of rows and ALL C columns,
@@ -1051,13 +1072,12 @@ __global__ __launch_bounds__(256) void colsum_stage1_v4(const float* __restrict_
 // of latency instead of four -- 17-23 us -> see DESIGN_HISTORY B.11; the summation order differs between the two forms
 // only in the association of the partial rows, fixed per (RB, WAVES): results stay run-to-run identical.
 template <int WAVES>
-__global__ __launch_bounds__(64 * WAVES) void colsum_stage2(const float* __restrict__ ws, int RB, int nseg, int C,
-                                                            float* __restrict__ out, int64_t ldo, int accumulate,
-                                                            float scale) {
+__device__ __forceinline__ void colsum_stage2_body(const float* __restrict__ ws, int RB, int C, float* __restrict__ out,
+                                                   int64_t ldo, int accumulate, float scale, int s) {
   constexpr int UNR = WAVES == 16 ? 64 : 32;            // loads in flight per lane
   __shared__ float red[WAVES][64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = blockIdx.x * 64 + lane, s = blockIdx.y;
+  const int c = blockIdx.x * 64 + lane;
   float acc = 0.f;
   if (c < C) {
     float a32[UNR];
@@ -1087,6 +1107,17 @@ __global__ __launch_bounds__(64 * WAVES) void colsum_stage2(const float* __restr
     float* o = out + (int64_t)s * ldo + c;
     *o = accumulate ? *o + v : v;
   }
+}
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void colsum_stage2(const float* __restrict__ ws, int RB, int nseg, int C,
+                                                            float* __restrict__ out, int64_t ldo, int accumulate,
+                                                            float scale) {
+  colsum_stage2_body<WAVES>(ws, RB, C, out, ldo, accumulate, scale, blockIdx.y);
+}
+template <int WAVES>
+__global__ __launch_bounds__(64 * WAVES) void colsum_stage2_batch(ColsumBatch tab, const float* __restrict__ ws, int RB, int C) {
+  const int z = blockIdx.y;
+  colsum_stage2_body<WAVES>(ws + (int64_t)z * RB * C, RB, C, tab.out[z], C, 0, 1.0f, 0);
 }
 void launch_colsum_stage2(const float* ws, int RB, int nseg, int C, float* out, int64_t ldo, int accumulate, float scale,
                           int colblocks, hipStream_t st) {
@@ -1296,13 +1327,15 @@ extern "C" int tecm_gn_y16_supported(int32_t L, int32_t N, int32_t Cout) { retur
 
 extern "C" int tecm_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta, float* y,
                                   int64_t ldy, void* y16, int64_t ldy16, void* y16d, int64_t ldy16d, const TecmDrop* drop,
-                                  int32_t y16d_seq_T, int32_t y16d_seq_N, float* stats, int64_t M, int32_t D, float eps,
-                                  void* stream) {
+                                  int32_t y16d_seq_T, int32_t y16d_seq_N, int32_t y16d_f32, float* stats, int64_t M, int32_t D,
+                                  float eps, void* stream) {
   TECM_REQUIRE(x && gamma && beta && (y || y16 || y16d) && stats, TECM_E_ARG, "tecm_layernorm_fwd: null pointer");
   TECM_REQUIRE(y16d_seq_T == 0 || (y16d && y16d_seq_T > 0 && y16d_seq_N > 0 && M % ((int64_t)y16d_seq_T * y16d_seq_N) == 0),
                TECM_E_ARG, "tecm_layernorm_fwd: the sequence-major form needs y16d and M = B * T * N");
-  TECM_REQUIRE(!y16d || (tecm_aligned(y16d, 8) && ldy16d % 4 == 0 && ldy16d >= D), TECM_E_ALIGN,
-               "tecm_layernorm_fwd: the dropped bf16 output must be 8-byte aligned with a leading dimension multiple of 4");
+  TECM_REQUIRE(!y16d || (tecm_aligned(y16d, y16d_f32 ? 16 : 8) && ldy16d % 4 == 0 && ldy16d >= D), TECM_E_ALIGN,
+               "tecm_layernorm_fwd: the dropped output must be 8-byte (bf16) / 16-byte (fp32) aligned with a leading dimension "
+               "multiple of 4");
+  TECM_REQUIRE(!y16d_f32 || y16d, TECM_E_ARG, "tecm_layernorm_fwd: y16d_f32 goes with y16d");
   TECM_REQUIRE(!y16d || (drop && drop->p >= 0.f && drop->p < 1.f), TECM_E_ARG, "tecm_layernorm_fwd: y16d needs its dropout spec");
   const DropCtxN dd = make_dropn(y16d ? drop : nullptr);
   TECM_REQUIRE(!y16 || (tecm_aligned(y16, 8) && ldy16 % 4 == 0 && ldy16 >= D), TECM_E_ALIGN,
@@ -1317,7 +1350,7 @@ extern "C" int tecm_layernorm_fwd(const float* x, int64_t ldx, const float* gamm
   hipStream_t st = (hipStream_t)stream;
 #define LN_FWD(NCH) \
   hipLaunchKernelGGL((layernorm_fwd_kernel<NCH>), grid, dim3(256), 0, st, x, ldx, gamma, beta, y, ldy, y16, ldy16, y16d, ldy16d, \
-                     dd, stats, M, D, eps, (int)y16d_seq_T, (int)y16d_seq_N)
+                     dd, stats, M, D, eps, (int)y16d_seq_T, (int)y16d_seq_N, (int)(y16d_f32 != 0))
   switch (nch) {
     case 1: LN_FWD(1); break;
     case 2: LN_FWD(2); break;
@@ -1333,7 +1366,7 @@ extern "C" int tecm_layernorm_bwd(const float* dy, int64_t lddy, const float* x,
                                   const float* stats, const float* dres, float* dx, void* dx_masked,
                                   int32_t masked_bf16, const TecmDrop* mask_drop, float* dgb_partials,
                                   int32_t* num_blocks, int64_t M, int32_t D, const TecmLnAdd* add, int32_t dy_bf16,
-                                  const TecmLnDyMap* dymap, void* stream) {
+                                  const TecmLnDyMap* dymap, int32_t skip_dx, void* stream) {
   TECM_REQUIRE(M > 0 && D > 0 && D % 4 == 0 && D <= 256 * LN_MAXCH, TECM_E_ARG, "tecm_layernorm_bwd: bad M/D");
   const int nb = ln_blocks(M);
   if (num_blocks) *num_blocks = nb;
@@ -1356,14 +1389,20 @@ extern "C" int tecm_layernorm_bwd(const float* dy, int64_t lddy, const float* x,
  LnDyMap dm{};
   const bool has_map = dymap != nullptr && dymap->T > 0;
   if (has_map) {
-    TECM_REQUIRE(dy_bf16 && !has_add && dymap->N > 0 && M % ((int64_t)dymap->T * dymap->N) == 0, TECM_E_ARG,
-                 "tecm_layernorm_bwd: the sequence-major dy is a bf16 matrix of M = B * T * N rows, without a second stream");
+    TECM_REQUIRE(!has_add && dymap->N > 0 && M % ((int64_t)dymap->T * dymap->N) == 0, TECM_E_ARG,
+                 "tecm_layernorm_bwd: the sequence-major dy is a matrix of M = B * T * N rows, without a second stream");
     dm.T = dymap->T; dm.N = dymap->N; dm.drop = make_dropn(&dymap->drop);
   }
+  // skip_dx: the unmasked dx has no reader (dx_masked is the only output): its store is left out, dx is not touched
+  TECM_REQUIRE(!skip_dx || dx_masked, TECM_E_ARG, "tecm_layernorm_bwd: skip_dx needs dx_masked");
+  if (skip_dx) dx = nullptr;
 #define LN_BWD(NCH)                                                                                                       \
   do {                                                                                                                    \
-    if (has_map)                                                                                                          \
+    if (has_map && dy_bf16)                                                                                               \
       hipLaunchKernelGGL((layernorm_bwd_kernel<NCH, false, true, true>), dim3(nb), dim3(256), 0, st, dy, lddy, x, ldx, gamma, \
+                         stats, dres, dx, static_cast<float*>(dx_masked), (int)masked_bf16, odc, dgb_partials, M, D, ad, dm); \
+    else if (has_map)                                                                                                     \
+      hipLaunchKernelGGL((layernorm_bwd_kernel<NCH, false, false, true>), dim3(nb), dim3(256), 0, st, dy, lddy, x, ldx, gamma, \
                          stats, dres, dx, static_cast<float*>(dx_masked), (int)masked_bf16, odc, dgb_partials, M, D, ad, dm); \
     else if (has_add && dy_bf16)                                                                                               \
       hipLaunchKernelGGL((layernorm_bwd_kernel<NCH, true, true>), dim3(nb), dim3(256), 0, st, dy, lddy, x, ldx, gamma, stats, \
@@ -1678,4 +1717,46 @@ extern "C" int tecm_colsum_twin(const float* in, int64_t ld, int64_t outer, int6
   TECM_REQUIRE(twin_bf16 && ld_twin >= C && ld_twin % 4 == 0 && tecm_aligned(twin_bf16, 8), TECM_E_ARG,
                "tecm_colsum_twin: the bf16 twin needs 8-byte friendly rows of at least C values");
   return colsum_impl(in, ld, outer, inner, nseg, C, out, ldo, accumulate, scale, in_drop, workspace, twin_bf16, ld_twin, stream);
+}
+
+// out[i][c] = sum over rows of in[i][row*ld + c] for nbuf matrices of the same (rows, C) shape: the result of
+// tecm_colsum(in[i], ld, rows, 1, 1, C, out[i], C, 0, 1.0f, NULL, ...) on each -- the same blocks, row chunks and order of
+// every sum, bit for bit -- in one pair of launches for all of them (a grid dimension walks the pointer table, which
+// travels in the kernel arguments).  Shapes the float4 first stage serves (C <= 1024) are reduced matrix by matrix.
+extern "C" int tecm_colsum_batch(const float* const* in, float* const* out, int32_t nbuf, int64_t ld, int64_t rows, int32_t C,
+                                 float* workspace, void* stream) {
+  TECM_REQUIRE(in && out && workspace && nbuf > 0 && rows > 0 && C > 0 && ld >= C, TECM_E_ARG, "tecm_colsum_batch: bad arguments");
+  for (int i = 0; i < nbuf; ++i) TECM_REQUIRE(in[i] && out[i], TECM_E_ARG, "tecm_colsum_batch: null matrix %d", i);
+  const int colblocks = (C + 63) / 64;
+  bool any4 = false;                // would tecm_colsum take its float4 first stage for one of the matrices?
+  if (C % 4 == 0 && C <= 1024 && ld % 4 == 0 && tecm_aligned(workspace, 16))
+    for (int i = 0; i < nbuf; ++i) any4 = any4 || tecm_aligned(in[i], 16);
+  if (any4) {                       // then every matrix goes through tecm_colsum's own choice, one by one
+    for (int i = 0; i < nbuf; ++i) {
+      const int rc = colsum_impl(in[i], ld, rows, 1, 1, C, out[i], C, 0, 1.0f, nullptr, workspace, nullptr, 0, stream);
+      if (rc != TECM_OK) return rc;
+    }
+    return TECM_OK;
+  }
+  int64_t rb = 1024 / (int64_t)colblocks;               // as colsum_impl with nseg = 1
+  if (rb > 256) rb = 256;
+  if (rb > (rows + 15) / 16) rb = (rows + 15) / 16;
+  if (rb < 1) rb = 1;
+  const int64_t chunk = (rows + rb - 1) / rb;
+  rb = (rows + chunk - 1) / chunk;
+  hipStream_t st = (hipStream_t)stream;
+  for (int i0 = 0; i0 < nbuf; i0 += COLSUM_BATCH_MAX) {
+    const int n = nbuf - i0 < COLSUM_BATCH_MAX ? nbuf - i0 : COLSUM_BATCH_MAX;
+    ColsumBatch tab{};
+    for (int i = 0; i < n; ++i) { tab.in[i] = in[i0 + i]; tab.out[i] = out[i0 + i]; }
+    float* ws = workspace + (int64_t)i0 * rb * C;
+    hipLaunchKernelGGL(colsum_stage1_batch, dim3(colblocks, (unsigned)rb, n), dim3(256), 0, st, tab, ld, rows, C, ws, chunk);
+    TECM_CHECK_LAUNCH("tecm_colsum_batch/stage1");
+    if (colblocks <= 4 && rb > 256)
+      hipLaunchKernelGGL(colsum_stage2_batch<16>, dim3(colblocks, n), dim3(1024), 0, st, tab, ws, (int)rb, C);
+    else
+      hipLaunchKernelGGL(colsum_stage2_batch<8>, dim3(colblocks, n), dim3(512), 0, st, tab, ws, (int)rb, C);
+    TECM_CHECK_LAUNCH("tecm_colsum_batch/stage2");
+  }
+  return TECM_OK;
 }

@@ -40,6 +40,11 @@ def _fuse_head() -> bool:
     """TECM_FUSE_HEAD=0: ln_f and the head as separate stages (A/B diagnostics)."""
     return os.environ.get("TECM_FUSE_HEAD", "1") != "0"
 
+
+def _embd_masked_grad() -> bool:
+    """TECM_EMBD_MASKED_GRAD=0: the patch projection's backward masks the gradient of h0 itself (A/B diagnostics)."""
+    return os.environ.get("TECM_EMBD_MASKED_GRAD", "1") != "0"
+
 _REQUIRED = ("num_nodes", "d_emb", "spatial_in_channels_base", "spatial_out_channels", "spatial_heads",
              "temporal_channel_list", "temporal_strides", "patch_len", "d_llm", "llm_layers", "temporal_seq_len",
              "prediction_horizon")
@@ -110,8 +115,9 @@ class TEC_MoLLM(nn.Module):
             return 0
         cfg = self.model_config
         key = ("model", self._cfg_key, B, int(precision), self.training, grad)
-        fuse = _fuse_head()
-        return mem_.choose(key, lambda lv: mem_.estimate(cfg, B, int(precision), lv, self.training, grad, fuse_head=fuse),
+        fuse, emg = _fuse_head(), _embd_masked_grad()
+        return mem_.choose(key, lambda lv: mem_.estimate(cfg, B, int(precision), lv, self.training, grad, fuse_head=fuse,
+                                                         embd_masked_grad=emg),
                            self.prediction_head.mlp[0].weight.device, what="TEC_MoLLM.forward")
 
     def forward(self, x: torch.Tensor, time_features: torch.Tensor, edge_index: torch.Tensor,
@@ -138,10 +144,15 @@ class TEC_MoLLM(nn.Module):
                                 *self.spatial_encoder.params(), meta, self.heads, R, plan)
         # 5. temporal encoder (+ wpe and embd dropout of the GPT-2 front end) -> (B, P, N, 768)
         wpe = self.llm_backbone.trunk.wpe.weight
+        # (outside bf16 mode the gradient of h0 comes back already masked by the embd dropout applied here: layer 0's
+        #  LayerNorm backward writes the masked gradient alone, F_.GPT2StackFn / F_.PatchEmbedFn)
+        if int(plan.bf16) != F_.ops.PREC_BF16 and _embd_masked_grad():
+            plan = dataclasses.replace(plan, embd_masked_grad=True)
         h0 = self.temporal_encoder.forward_tm(xs, self.c_spatial, wpe, plan, need_dinp=True)
         # 6. GPT-2 blocks with LoRA; 7. dropout + prediction head -> (B, N, L_out)
-        # (bf16 mode: ln_f hands the head its operand directly -- dropped, rounded, sequence-major; F_.GPT2StackFn)
-        if int(plan.bf16) == F_.ops.PREC_BF16 and _fuse_head():
+        # (bf16 and fp32 mode: ln_f hands the head its operand directly -- dropped, rounded in bf16 mode, sequence-major;
+        #  F_.GPT2StackFn)
+        if int(plan.bf16) in (F_.ops.PREC_BF16, F_.ops.PREC_FP32) and _fuse_head():
             plan = dataclasses.replace(plan, fuse_head=True)
         hid = self.llm_backbone.forward_tm(h0, plan)
         pred = self.prediction_head.forward_tm(hid, plan)

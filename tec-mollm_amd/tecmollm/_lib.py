@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TECM_LIB", os.path.join(_HERE, "libtecmollm_hip.so"))   # override for experiments
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 c_f32p = C.c_void_p
 
@@ -184,11 +184,11 @@ EXPORTS = {
                                           C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, c_f32p, C.c_void_p]),
     "tecm_layernorm_fwd": (C.c_int, [c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_void_p, C.c_int64,
-                                     C.c_void_p, C.c_int64, C.POINTER(TecmDrop), C.c_int32, C.c_int32,
+                                     C.c_void_p, C.c_int64, C.POINTER(TecmDrop), C.c_int32, C.c_int32, C.c_int32,
                                      c_f32p, C.c_int64, C.c_int32, C.c_float, C.c_void_p]),
     "tecm_layernorm_bwd": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
                                      C.c_int32, C.POINTER(TecmDrop), c_f32p, C.POINTER(C.c_int32), C.c_int64, C.c_int32,
-                                     C.POINTER(TecmLnAdd), C.c_int32, C.POINTER(TecmLnDyMap), C.c_void_p]),
+                                     C.POINTER(TecmLnAdd), C.c_int32, C.POINTER(TecmLnDyMap), C.c_int32, C.c_void_p]),
     "tecm_attention_fwd": (C.c_int, [c_f32p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.POINTER(TecmDrop), C.c_void_p]),
     "tecm_cast_bf16": (C.c_int, [c_f32p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p]),
@@ -198,6 +198,8 @@ EXPORTS = {
                               C.c_int32, C.c_float, C.POINTER(TecmDrop), c_f32p, C.c_void_p]),
     "tecm_colsum_twin": (C.c_int, [c_f32p, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_f32p, C.c_int64,
                                    C.c_int32, C.c_float, C.POINTER(TecmDrop), c_f32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "tecm_colsum_batch": (C.c_int, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int32, C.c_int64, C.c_int64, C.c_int32,
+                                    c_f32p, C.c_void_p]),
     "tecm_huber_fwd_bwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_float, C.c_float, c_f32p,
                                      C.c_void_p]),
     "tecm_huber_fwd_bwd_strided": (C.c_int, [c_f32p, C.POINTER(C.c_int64), c_f32p, C.POINTER(C.c_int64), c_f32p, c_f32p,

@@ -25,6 +25,16 @@ PRE16 = os.environ.get("TECM_PRE16", "1")[:1] != "0"     # diagnostics: "0" keep
 GRAD16 = os.environ.get("TECM_GRAD16", "1")[:1] != "0"   # diagnostics: "0" keeps d LN-out / d ctx fp32 in bf16 mode
 QKV16 = os.environ.get("TECM_QKV16", "1")[:1] != "0"   # diagnostics: "0" keeps qkv fp32 in bf16 mode
 
+
+def _split_dcattn() -> bool:
+    """TECM_SPLIT_DCATTN=0: fp32 d c_attn (+ d z) as ONE K-extended launch of N = 800 (A/B diagnostics)."""
+    return os.environ.get("TECM_SPLIT_DCATTN", "1") != "0"
+
+
+def _ln_batch_reduce() -> bool:
+    """TECM_LN_BATCH_REDUCE=0: every LayerNorm backward of the GPT-2 stack reduces its own partials (A/B diagnostics)."""
+    return os.environ.get("TECM_LN_BATCH_REDUCE", "1") != "0"
+
 import ctypes as C
 
 CP = 24            # C = 22 feature channels padded to a multiple of 4 floats (16-byte rows)
@@ -60,7 +70,11 @@ class DropPlan:
     p: float
     base_seed: int
     bf16: bool = False      # run the dense contractions on the bf16 matrix cores (autocast semantics)
-    fuse_head: bool = False  # bf16 mode, whole model: ln_f writes the head's operand directly (see GPT2StackFn / HeadFn)
+    fuse_head: bool = False  # whole model, bf16 or fp32: ln_f writes the head's operand directly (see GPT2StackFn / HeadFn)
+    # whole model, not bf16 mode: the gradient GPT2StackFn returns for h0 already carries the embd-dropout mask of
+    # PatchEmbedFn's forward epilogue (layer 0's LayerNorm backward applies it), so PatchEmbedFn.backward does not
+    # apply it again
+    embd_masked_grad: bool = False
     # activation recomputation (tecmollm/memory.py picks it): 0 = every stage keeps what its backward reads; 1 = the GPT-2
     # blocks keep their input h only and re-run their forward in the backward; 2 = 1 + the conv blocks keep their input only
     recompute: int = 0
@@ -584,6 +598,9 @@ class PatchEmbedFn(torch.autograd.Function):
         #  weight gradient runs on the natural-orientation LDS-DMA kernel; the column sums keep the fp32 values)
         t16 = int(plan.bf16) == ops.PREC_BF16 and conv.dtype == torch.bfloat16 and \
             ops.tn_ok(d_llm, K, M) and d_llm % 8 == 0
+        if plan.embd_masked_grad and (t16 or not has_wpe):
+            raise _lib_error("PatchEmbedFn: embd_masked_grad is the whole model's contract outside bf16 mode (the gradient "
+                             "arrives masked by the embd dropout PatchEmbedFn applied)")
         dh16 = None
         cdrop = None                                       # mask the column sums apply to dh0 on the fly
         if t16:
@@ -591,7 +608,7 @@ class PatchEmbedFn(torch.autograd.Function):
             # gradients) and written as the bf16 tensor the two GEMMs read; the fp32 masked gradient is never materialised
             dh16 = torch.empty(M, d_llm, device=dh0.device, dtype=torch.bfloat16)
             cdrop = dspec
-        elif dspec is not None:
+        elif dspec is not None and not plan.embd_masked_grad:
             dh0 = ops.dropout_apply(dh0, M, d_llm, dspec)
         dwpe = None
         if has_wpe:
@@ -739,9 +756,12 @@ class GPT2StackFn(torch.autograd.Function):
         # (tec_mollm.py:115, modules.py:307), a bf16 contraction over view(B*N, T*D).  ln_f then writes exactly that operand:
         # dropout applied, rounded to bf16, rows in sequence-major order -- no fp32 ln_f output, no dropout pass, no window view
         # in the head GEMMs; the gradient comes back in the same form and ln_f's backward applies the mask (round 4).
-        ctx.fused = bool(plan.fuse_head) and int(plan.bf16) == ops.PREC_BF16 and D % 8 == 0
+        # fp32 mode: the same, unrounded -- the fp32 matrix dropout_apply + the head's window view would present, bit for bit
+        ctx.fused = bool(plan.fuse_head) and ((int(plan.bf16) == ops.PREC_BF16 and D % 8 == 0) or
+                                              int(plan.bf16) == ops.PREC_FP32)
         if ctx.fused:
-            out = torch.empty(B, N, T * D, device=h.device, dtype=torch.bfloat16)
+            out = torch.empty(B, N, T * D, device=h.device,
+                              dtype=torch.bfloat16 if int(plan.bf16) == ops.PREC_BF16 else torch.float32)
             pspec = plan.spec(SITE_POST, D)
             ops.layernorm_fwd(h, D, lnfw, lnfb, None, D, stf, M, D, y16d=out, ldy16d=D,
                               drop16d=pspec if pspec is not None else ops.NO_DROP, seq_major=(T, N))
@@ -885,10 +905,21 @@ class GPT2StackFn(torch.autograd.Function):
         dhm = masked_buf(sp, last_Wpr) if sp is not None else dh
         nig = ctx.needs_input_grad                        # (h0, n_layers, plan, *params): params start at index 3
         base_f = 3 + n_layers * GPT2StackFn.PER_LAYER
-        dlnfw, dlnfb = ops.layernorm_bwd(dout, D, h_last, D, lnfw, stf, None, dh, M, D,
-                                         dx_masked=dhm if sp is not None else None, mask_drop=sp,
-                                         need_dgb=nig[base_f] or nig[base_f + 1],
-                                         dy_seq_major=(T, N, plan.spec(SITE_POST, D)) if ctx.fused else None)
+        # the gamma / beta partials of the 2 * layers + 1 LayerNorm backwards (one (blocks, 2D) buffer each) are collected and
+        # reduced by ONE launch pair at the end instead of a colsum pair per LayerNorm: same sums, same order
+        parts: Optional[list] = [] if _ln_batch_reduce() else None
+        part_slots: List[int] = []                        # index into pgrads of each collected buffer's gamma (-1: ln_f)
+
+        def ln_bwd(slot, need, *a, **k):
+            g_, b_ = ops.layernorm_bwd(*a, need_dgb=need, partials_out=parts, **k)
+            if parts is not None and need:
+                part_slots.append(slot)
+            return g_, b_
+
+        dlnfw, dlnfb = ln_bwd(-1, nig[base_f] or nig[base_f + 1], dout, D, h_last, D, lnfw, stf, None, dh, M, D,
+                              dx_masked=dhm if sp is not None else None, mask_drop=sp,
+                              dy_seq_major=(T, N, plan.spec(SITE_POST, D)) if ctx.fused else None,
+                              dy_seq_fp32=ctx.fused and dout.dtype == torch.float32)
         pgrads: List[Optional[torch.Tensor]] = [None] * (n_layers * GPT2StackFn.PER_LAYER)
         for i in reversed(range(n_layers)):
             (ln1w, ln1b, Wqkv, bqkv, lA, lB, Wo, bo, ln2w, ln2b, Wfc, bfc, Wpr,
@@ -925,9 +956,8 @@ class GPT2StackFn(torch.autograd.Function):
             sp = plan.spec(site_res1(i), D)
             dh2m = masked_buf(sp, Wo) if sp is not None else dh2
             pb = 3 + i * GPT2StackFn.PER_LAYER
-            dg2, db2 = ops.layernorm_bwd(du2, D, h2, D, ln2w, st2, dh, dh2, M, D,
-                                         dx_masked=dh2m if sp is not None else None, mask_drop=sp,
-                                         need_dgb=nig[pb + 8] or nig[pb + 9])
+            dg2, db2 = ln_bwd(i * GPT2StackFn.PER_LAYER + 8, nig[pb + 8] or nig[pb + 9], du2, D, h2, D, ln2w, st2, dh, dh2, M, D,
+                              dx_masked=dh2m if sp is not None else None, mask_drop=sp)
             # attention: h2 = h + drop(ctx Wo + b)
             Wo_b = _bwd_weight(Wo, plan.bf16)
             c16 = g16 and Wo_b.dtype == torch.bfloat16 and dh2m.dtype == torch.bfloat16 and qkv.dtype == torch.bfloat16
@@ -941,7 +971,14 @@ class GPT2StackFn(torch.autograd.Function):
             ops.attention_bwd(qkv, dcx, dqkv, B, T, N, GPT_HEADS, D, plan.spec(site_attn(i), 1))
             u16g = g16 and q16 and u.dtype == torch.bfloat16
             du = torch.empty(M, KE, device=dh.device, dtype=torch.bfloat16 if u16g else torch.float32)   # [ d LN1-out | dz ]
-            gemm(M, KE, F3, dqkv, F3, wcat, F3, du, KE, bf16=plan.bf16)
+            if int(plan.bf16) == ops.PREC_FP32 and _split_dcattn():
+                # fp32: N = 800 is 7 tile columns of 128 with 96 of the last 128 dead.  The 768 base columns run as six full
+                # tile columns, the 32 LoRA columns (dz) as a launch of the 32-wide tile on a second read of dqkv; every
+                # element is the same sum over k in the same order
+                gemm(M, D, F3, dqkv, F3, wcat, F3, du, KE, bf16=plan.bf16)
+                gemm(M, LORA_R, F3, dqkv, F3, wcat, F3, du, KE, b_off=D * F3, c_off=D, bf16=plan.bf16)
+            else:
+                gemm(M, KE, F3, dqkv, F3, wcat, F3, du, KE, bf16=plan.bf16)
             lspec = plan.spec(site_lora(i), KE)
             dlB = _empty(F3, LORA_R, like=dh)
             gemm(F3, LORA_R, M, dqkv, F3, u, KE, dlB, LORA_R, a_layout=A_KM, b_layout=B_KN, b_off=D,
@@ -962,13 +999,18 @@ class GPT2StackFn(torch.autograd.Function):
                 gemm(M, D, LORA_R, du, KE, ctx.lAT16[i], LORA_R, dzA, D, a_off=D, bf16=plan.bf16)     # [row][k] operands: LDS-DMA
             else:
                 gemm(M, D, LORA_R, du, KE, lA, D, dzA, D, b_layout=B_KN, a_off=D, bf16=plan.bf16)
-            dhn = _empty(M, D, like=dh)
-            sp = plan.spec(site_res2(i - 1), D) if i > 0 else None
-            dhm = masked_buf(sp, params[(i - 1) * GPT2StackFn.PER_LAYER + 12]) if sp is not None else dhn
-            dg1, db1 = ops.layernorm_bwd(du, KE, h, D, ln1w, st1, dh2, dhn, M, D,
-                                         dx_masked=dhm if sp is not None else None, mask_drop=sp,
-                                         need_dgb=nig[pb + 0] or nig[pb + 1],
-                                         add=(dzA, D, lspec))
+            # layer 0 inside the whole model (plan.embd_masked_grad): the stack's input gradient has ONE reader, the patch
+            # projection's backward, behind the embd dropout of its forward epilogue -- it leaves as the masked gradient alone
+            sp = plan.spec(site_res2(i - 1), D) if i > 0 else (plan.spec(SITE_EMBD, D) if plan.embd_masked_grad else None)
+            only_masked = i == 0 and sp is not None
+            if only_masked:
+                dhn = dhm = _empty(M, D, like=dh)
+            else:
+                dhn = _empty(M, D, like=dh)
+                dhm = masked_buf(sp, params[(i - 1) * GPT2StackFn.PER_LAYER + 12]) if sp is not None else dhn
+            dg1, db1 = ln_bwd(i * GPT2StackFn.PER_LAYER, nig[pb + 0] or nig[pb + 1], du, KE, h, D, ln1w, st1, dh2, dhn, M, D,
+                              dx_masked=dhm if sp is not None else None, mask_drop=sp,
+                              add=(dzA, D, lspec), skip_dx=only_masked)
             dh = dhn
             base = i * GPT2StackFn.PER_LAYER
             pgrads[base + 0], pgrads[base + 1] = dg1, db1
@@ -976,6 +1018,17 @@ class GPT2StackFn(torch.autograd.Function):
             pgrads[base + 8], pgrads[base + 9] = dg2, db2
             if ctx.level:                                 # the rebuilt block and its gradients' working set
                 del u, ud, st1, qkv, h2, st2, a, du2, dh2, dh2m, dcx, dqkv, du, dzA
+            elif parts is not None:
+                # the collected partials now live until the end of the backward: dzA (dead here, M x D) goes before the
+                # next block's working set is allocated, so that the step's peak does not rise by them
+                del dzA
+        if parts:
+            red = ops.colsum_batch(parts, parts[0].shape[0], 2 * D)
+            for r, slot in enumerate(part_slots):
+                if slot < 0:
+                    dlnfw, dlnfb = red[r, :D], red[r, D:]
+                else:
+                    pgrads[slot], pgrads[slot + 1] = red[r, :D], red[r, D:]
         pg = [g if ctx.needs_input_grad[3 + j] else None for j, g in enumerate(pgrads)]
         return (dh.view(B, T, N, D), None, None, *pg, dlnfw, dlnfb)
 
@@ -987,7 +1040,7 @@ class HeadFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, hid, W1, b1, W2, b2, plan: DropPlan):
-        ctx.fused = hid.dim() == 3 and hid.dtype == torch.bfloat16
+        ctx.fused = hid.dim() == 3 and (hid.dtype == torch.bfloat16 or bool(plan.fuse_head))
         if ctx.fused:
             return HeadFn._forward_fused(ctx, hid, W1, b1, W2, b2, plan)
         B, T, N, D = hid.shape
@@ -1018,13 +1071,17 @@ class HeadFn(torch.autograd.Function):
     @staticmethod
     def _forward_fused(ctx, hid, W1, b1, W2, b2, plan: DropPlan):
         """hid = bf16(F.dropout(ln_f(h))) as the plain (B, N, T*D) matrix GPT2StackFn wrote (plan.fuse_head): every head
-        contraction is a plain one over bf16 tensors -- W1 and W1^T rounded once per step (tecm_weight_bf16)."""
+        contraction is a plain one over bf16 tensors -- W1 and W1^T rounded once per step (tecm_weight_bf16).
+        fp32 mode: hid = F.dropout(ln_f(h)) in the same form, fp32; the contractions read it and W1 as they are."""
         B, N, K1 = hid.shape
         S = B * N
         Hd = W1.shape[0]
         Lo = W2.shape[0]
         hspec = plan.spec(SITE_HEAD, Hd)
-        W1_16, W1T16 = ops.weight_bf16(W1, same=True, transposed=True)
+        if hid.dtype == torch.bfloat16:
+            W1_16, W1T16 = ops.weight_bf16(W1, same=True, transposed=True)
+        else:
+            W1_16, W1T16 = W1, None
         pre = _empty(S, Hd, like=hid)
         h1 = _empty(S, Hd, like=hid)
         gemm(S, Hd, K1, hid, K1, W1_16, K1, h1, Hd, bias=b1, preact=(pre, Hd), act=ACT_GELU_ERF, out_drop=hspec, bf16=plan.bf16)
@@ -1049,15 +1106,24 @@ class HeadFn(torch.autograd.Function):
         dpre = _empty(S, Hd, like=hid)
         gemm(S, Hd, Lo, dpred, Lo, W2, Hd, dpre, Hd, b_layout=B_KN, act=ACT_GELU_ERF, dact_src=(pre, Hd),
              out_drop=hspec, bf16=plan.bf16)
-        dp = torch.empty(S, Hd, device=hid.device, dtype=torch.bfloat16)     # what both contractions round dpre to, written by
-        db1 = colsum(dpre, Hd, S, 1, 1, Hd, twin=dp)[0]                      # the pass that sums the fp32 values into db1
+        f32 = hid.dtype == torch.float32
+        if f32:
+            dp = dpre
+            db1 = colsum(dpre, Hd, S, 1, 1, Hd)[0]
+        else:
+            dp = torch.empty(S, Hd, device=hid.device, dtype=torch.bfloat16)     # what both contractions round dpre to, written
+            db1 = colsum(dpre, Hd, S, 1, 1, Hd, twin=dp)[0]                      # by the pass that sums the fp32 values into db1
         dW1 = _empty(Hd, K1, like=hid)
         gemm(Hd, K1, S, dp, Hd, hid, K1, dW1, K1, a_layout=A_KM, b_layout=B_KN,
              split_k=pick_split_k(Hd, K1, S, prec=plan.bf16), bf16=plan.bf16)
         # the gradient a bf16 Linear returns for its input is a bf16 tensor under autocast (train.py:68): stored as such, in
         # the operand's own (sequence-major) layout; ln_f's backward applies the dropout mask and the layout
-        dhid = torch.empty(B, N, K1, device=hid.device, dtype=torch.bfloat16)
-        gemm(S, K1, Hd, dp, Hd, ctx.W1T16, Hd, dhid, K1, bf16=plan.bf16)
+        # (fp32 mode: the fp32 gradient in that layout, likewise still in front of the mask)
+        dhid = torch.empty(B, N, K1, device=hid.device, dtype=hid.dtype)
+        if f32:
+            gemm(S, K1, Hd, dp, Hd, W1, K1, dhid, K1, b_layout=B_KN, bf16=plan.bf16)
+        else:
+            gemm(S, K1, Hd, dp, Hd, ctx.W1T16, Hd, dhid, K1, bf16=plan.bf16)
         return dhid, dW1, db1, dW2, db2, None
 
     @staticmethod

@@ -180,6 +180,8 @@ def _stack_bwd(s: _Sim, M: int, n_layers: int, prec: int, training: bool, level:
         if level:
             s.drop_prefix(tag + ".")
             s.drop("bw.du2", "bw.dh2", "bw.dh2m", "bw.dcx", "bw.dqkv", "bw.du", "bw.dzA")
+        # (level 0 with the batched gamma / beta reduction drops dzA here as well and keeps the (blocks, 2D) partials of every
+        #  LayerNorm -- 6 MB each -- to the end instead: the estimate counts neither and stays an upper bound by 4 M D bytes)
     s.drop_prefix("stack.keep.")
     s.drop_prefix("stack.h")
     s.drop("bw.du2", "bw.dh2", "bw.dh2m", "bw.dcx", "bw.dqkv", "bw.du", "bw.dzA", "bw.dhm", dout)
@@ -238,10 +240,12 @@ def _trainable_bytes(cfg: dict, T: int, N: int) -> int:
     return 4 * n
 
 
-def estimate(cfg: dict, B: int, prec: int, level: int, training: bool, grad: bool, fuse_head: bool = True) -> Estimate:
+def estimate(cfg: dict, B: int, prec: int, level: int, training: bool, grad: bool, fuse_head: bool = True,
+             embd_masked_grad: bool = True) -> Estimate:
     """Bytes one TEC_MoLLM step allocates on top of what exists before it (parameters, optimizer state, cached weight
     copies).  cfg: the model_config dict; prec: ops.PREC_*; training: model.training (dropout on); grad: a backward follows
-    (False: the lean forward of functions.DropPlan.keep = False, whatever the level)."""
+    (False: the lean forward of functions.DropPlan.keep = False, whatever the level).  fuse_head / embd_masked_grad: the
+    DropPlan fields of the same names as TEC_MoLLM.forward sets them (bf16 and fp32 mode / every mode but bf16)."""
     from . import functions as F_
     prec = int(prec)
     N = int(cfg["num_nodes"])
@@ -252,7 +256,8 @@ def estimate(cfg: dict, B: int, prec: int, level: int, training: bool, grad: boo
     S, K1, Hd, Lout = _head_dims(cfg, B, N, T)
     keep = bool(grad)
     lv = level if keep else 0
-    fused = fuse_head and prec == 1
+    fused16 = fuse_head and prec == 1                   # ln_f writes the head's operand: bf16 ...
+    fused = fused16 or (fuse_head and prec == 0)        # ... or fp32 (same bytes as ln_f's plain output, no dropped copy)
     s = _Sim()
     # ---- forward
     s.new("xs", B * L * N * F_.CP * 4)                                        # SpatialFn output
@@ -277,12 +282,12 @@ def estimate(cfg: dict, B: int, prec: int, level: int, training: bool, grad: boo
         s.drop(cur)                                                           # the projection keeps the bf16 copy, if any
     if not keep and cur16 is not None:
         s.drop(cur16)
-    _stack_fwd(s, M, S, int(cfg["llm_layers"]), prec, training, lv, keep, fused, "h0")
+    _stack_fwd(s, M, S, int(cfg["llm_layers"]), prec, training, lv, keep, fused16, "h0")
     # head
-    if fused:
+    if fused16:
         s.new("hd.w1_16", Hd * K1 * 2)
         s.new("hd.w1t16", Hd * K1 * 2)
-    elif training:
+    elif training and not fused:
         s.new("hd.hd", M * D_LLM * (2 if prec == 1 else 4))
     s.new("hd.pre", S * Hd * 4)
     s.new("hd.h1", S * Hd * 4)
@@ -296,17 +301,17 @@ def estimate(cfg: dict, B: int, prec: int, level: int, training: bool, grad: boo
     # ---- backward (TrainStep: the returned gradients stay alive until the flat buffer absorbs them)
     s.new("grads", _trainable_bytes(cfg, T, N))
     s.new("hb.dpre", S * Hd * 4)
-    if fused or (prec == 1 and training):                                     # the bf16 twin of dpre, and W1^T in bf16
+    if fused16 or (prec == 1 and training):                                   # the bf16 twin of dpre, and W1^T in bf16
         s.new("hb.dp", S * Hd * 2)
     if prec == 1 and training and not fused:
         s.new("hb.w1t16", Hd * K1 * 2)
-    s.new("hb.dhid", M * D_LLM * (2 if fused else 4))
+    s.new("hb.dhid", M * D_LLM * (2 if fused16 else 4))
     s.drop("hb.dpre", "hb.dp", "hb.w1t16", "hd.pre", "hd.h1", "hd.hd", "hd.w1t16", "stack.out")
     _stack_bwd(s, M, int(cfg["llm_layers"]), prec, training, lv, "hb.dhid")
     # patch projection
     if prec == 1:
         s.new("pb.dh16", M * D_LLM * 2)
-    elif training:
+    elif training and not embd_masked_grad:                                   # else the stack's gradient arrives masked
         s.new("pb.dhm", M * D_LLM * 4)
     last = blocks[-1]
     s.new("pb.dconv", last["out"])

@@ -4,7 +4,7 @@ from __future__ import annotations
 
 import os
 import ctypes as C
-from typing import Optional, Tuple
+from typing import List, Optional, Tuple
 
 import torch
 
@@ -241,17 +241,19 @@ def layernorm_fwd(x: torch.Tensor, ldx: int, gamma: torch.Tensor, beta: torch.Te
     """y (fp32) and / or y16 (bf16 copy for a bf16 matrix-core GEMM, BASELINE configs[2]); y16d: a third, optional bf16
     output = dropout(y, drop16d) rounded -- the LoRA branch's input (peft lora_dropout, modules.py:181).  seq_major = (T, N):
     y16d is written sequence-major -- row (b, n, t) for the time-major row (b, t, n) -- the head's view(batch, -1) of ln_f's
-    (dropped) output as a plain matrix; drop16d may then be NO_DROP (eval mode)."""
-    for t, what in ((y16, "y16"), (y16d, "y16d")):
-        if t is not None and t.dtype != torch.bfloat16:
-            raise _lib.TecmError(f"layernorm_fwd: {what} must be a bfloat16 tensor")
+    (dropped) output as a plain matrix; drop16d may then be NO_DROP (eval mode).  y16d may also be an fp32 tensor: the dropped
+    output unrounded (fp32 mode's head operand), the values dropout_apply makes of y."""
+    if y16 is not None and y16.dtype != torch.bfloat16:
+        raise _lib.TecmError("layernorm_fwd: y16 must be a bfloat16 tensor")
+    if y16d is not None and y16d.dtype not in (torch.bfloat16, torch.float32):
+        raise _lib.TecmError("layernorm_fwd: y16d must be a bfloat16 or float32 tensor")
     if y16d is not None and drop16d is None:
         raise _lib.TecmError("layernorm_fwd: y16d needs its dropout spec")
     sT, sN = seq_major if seq_major is not None else (0, 0)
     check(lib().tecm_layernorm_fwd(x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(),
                                    None if y is None else _off(y, y_off), ldy, ptr(y16), ldy16, ptr(y16d), ldy16d,
                                    C.byref(drop16d) if drop16d is not None else None, sT, sN,
-                                   stats.data_ptr(), M, D, eps, stream_ptr()), "tecm_layernorm_fwd")
+                                   1 if (y16d is not None and y16d.dtype == torch.float32) else 0, stats.data_ptr(), M, D, eps, stream_ptr()), "tecm_layernorm_fwd")
 
 
 def _ln_add(add) -> Optional["_lib.TecmLnAdd"]:
@@ -268,19 +270,29 @@ def _ln_add(add) -> Optional["_lib.TecmLnAdd"]:
 def layernorm_bwd_blocks(M: int, D: int) -> int:
     nb = C.c_int32(0)
     check(lib().tecm_layernorm_bwd(None, 0, None, 0, None, None, None, None, None, 0, None, None, C.byref(nb), M, D,
-                                   None, 0, None, None), "tecm_layernorm_bwd(query)")
+                                   None, 0, None, 0, None), "tecm_layernorm_bwd(query)")
     return nb.value
 
 
 def layernorm_bwd(dy: torch.Tensor, lddy: int, x: torch.Tensor, ldx: int, gamma: torch.Tensor, stats: torch.Tensor,
                   dres: Optional[torch.Tensor], dx: torch.Tensor, M: int, D: int,
                   dx_masked: Optional[torch.Tensor] = None,
-                  mask_drop: Optional[TecmDrop] = None, need_dgb: bool = True, add=None, dy_seq_major=None):
+                  mask_drop: Optional[TecmDrop] = None, need_dgb: bool = True, add=None, dy_seq_major=None,
+                  skip_dx: bool = False, partials_out: Optional[list] = None, dy_seq_fp32: bool = False):
     """dx = dres + LN'(dy); optional dx_masked = dropout(dx, mask_drop) -- fp32, or bf16 when its only reader is a bf16
-    GEMM.  dy: fp32 or bf16.  dy_seq_major = (T, N, drop spec or None): dy is the bf16 sequence-major matrix (rows (b, n, t))
-    the head's first Linear returned, still in front of the post-LLM dropout whose mask is applied here.  add = (dy2, ld, drop): a second gradient stream of the same tensor, dy += dropmask * dy2 before
-    the LayerNorm backward (the LoRA branch's input gradient through lora_dropout's backward).  Returns (dgamma, dbeta), or
-    (None, None) when need_dgb is False (frozen LayerNorm: the per-block partials are not reduced)."""
+    GEMM.  dy: fp32 or bf16.  dy_seq_major = (T, N, drop spec or None): dy is the sequence-major matrix (rows (b, n, t), bf16
+    or fp32) the head's first Linear returned, still in front of the post-LLM dropout whose mask is applied here.  add =
+    (dy2, ld, drop): a second gradient stream of the same tensor, dy += dropmask * dy2 before the LayerNorm backward (the
+    LoRA branch's input gradient through lora_dropout's backward).  dy_seq_fp32 declares the sequence-major dy an fp32
+    matrix (fp32 mode's head); without it a sequence-major dy must be bf16 -- an upcast copy is refused.  skip_dx: dx_masked is the only output anybody reads --
+    the unmasked dx is not stored (the `dx` tensor is left untouched).  Returns (dgamma, dbeta), or (None, None) when
+    need_dgb is False (frozen LayerNorm: the per-block partials are not reduced).  partials_out: a list -- the (nb, 2*D)
+    partials buffer is appended to it INSTEAD of being reduced (when need_dgb), and (None, None) returned: the caller
+    reduces several of them in one launch (colsum_batch) and splits each row into (dgamma, dbeta)."""
+    if skip_dx and dx_masked is None:
+        raise _lib.TecmError("layernorm_bwd: skip_dx needs dx_masked")
+    if dy_seq_major is not None and (dy.dtype == torch.float32) != bool(dy_seq_fp32):
+        raise _lib.TecmError("layernorm_bwd: the sequence-major dy is a bf16 matrix, or an fp32 one declared by dy_seq_fp32")
     m16 = 1 if (dx_masked is not None and dx_masked.dtype == torch.bfloat16) else 0
     ad = _ln_add(add)
     dy16 = 1 if dy.dtype == torch.bfloat16 else 0        # bf16 mode: the gradient a bf16 GEMM returned for its input
@@ -295,9 +307,12 @@ def layernorm_bwd(dy: torch.Tensor, lddy: int, x: torch.Tensor, ldx: int, gamma:
     check(lib().tecm_layernorm_bwd(dy.data_ptr(), lddy, x.data_ptr(), ldx, gamma.data_ptr(), stats.data_ptr(),
                                    ptr(dres), dx.data_ptr(), ptr(dx_masked), m16, C.byref(od), partials.data_ptr(),
                                    C.byref(nbc), M, D, C.byref(ad) if ad is not None else None, dy16,
-                                   C.byref(dm) if dm is not None else None, stream_ptr()),
+                                   C.byref(dm) if dm is not None else None, 1 if skip_dx else 0, stream_ptr()),
           "tecm_layernorm_bwd")
     if not need_dgb:
+        return None, None
+    if partials_out is not None:
+        partials_out.append(partials)
         return None, None
     dgb = colsum(partials, 2 * D, nb, 1, 1, 2 * D)
     return dgb[0, :D], dgb[0, D:]
@@ -421,6 +436,21 @@ def colsum(inp: torch.Tensor, ld: int, outer: int, inner: int, nseg: int, Cn: in
         return out
     check(lib().tecm_colsum(_off(inp, in_off), ld, outer, inner, nseg, Cn, out.data_ptr(), Cn, 1 if accumulate else 0,
                             scale, C.byref(idr), ws.data_ptr(), stream_ptr()), "tecm_colsum")
+    return out
+
+
+def colsum_batch(mats: List[torch.Tensor], rows: int, Cn: int) -> torch.Tensor:
+    """(len(mats), Cn): row i = the column sums of the contiguous (rows, Cn) fp32 matrix mats[i] -- what
+    colsum(mats[i], Cn, rows, 1, 1, Cn) returns, bit for bit -- from one native call for all of them."""
+    n = len(mats)
+    for m in mats:
+        if m.dtype != torch.float32 or not m.is_contiguous() or m.numel() != rows * Cn:
+            raise _lib.TecmError("colsum_batch: every matrix is a contiguous fp32 (rows, Cn) tensor")
+    out = torch.empty(n, Cn, device=mats[0].device, dtype=torch.float32)
+    ws = torch.empty(max(1024, 256 * n) * Cn, device=out.device, dtype=torch.float32)     # contract: include/tecmollm.h
+    ins = (C.c_void_p * n)(*[m.data_ptr() for m in mats])
+    outs = (C.c_void_p * n)(*[out.data_ptr() + 4 * Cn * i for i in range(n)])
+    check(lib().tecm_colsum_batch(ins, outs, n, Cn, rows, Cn, ws.data_ptr(), stream_ptr()), "tecm_colsum_batch")
     return out
 
 

@@ -33,7 +33,7 @@ extern "C" {
 #define TECM_E_LAUNCH (-3)     /* hipGetLastError() != hipSuccess after the launch       */
 #define TECM_E_LDS (-4)        /* problem does not fit the 160 KiB LDS budget            */
 
-#define TECM_ABI_VERSION 20
+#define TECM_ABI_VERSION 21
 int tecm_abi_version(void);
 /* Human-readable text for the last error on this thread (host pointer, never NULL). */
 const char* tecm_last_error(void);
@@ -548,6 +548,38 @@ typedef struct {
   double* stats;
 } TecmMetrics;
 int tecm_metrics_accumulate(const TecmMetrics* m, void* stream);
+
+/* (3b) the same eight statistics per cell (g, h, i) -- group of the sample, horizon, node -- instead of per horizon:
+ * evaluate_metrics (src/evaluation/metrics.py:10-89) applied per cell, for error maps and for scores stratified by storm
+ * level or time of day.  The first fields are TecmMetrics' with the same meaning and the same value pipeline (non-finite
+ * scaled prediction -> 0, inverse transform with two f32 roundings, nan_to_num, optional clip of the prediction).
+ *   group  (S) int32 on the device: the group of every sample; NULL = every sample is in group 0.  A sample whose id is
+ *          outside [0, G) is skipped and sets TECM_BAD_GROUP in *err_flag (the device error word of TecmSpatial::err_flag:
+ *          never NULL, sticky, read back by tecmollm/devcheck.py); it is never clamped into a valid group.
+ *   stats  (G, H, 8, I) doubles, ((g*H + h)*8 + k)*I + i, ACCUMULATED across calls; node-contiguous, so that lanes owning
+ *          neighbouring nodes read and write neighbouring doubles.
+ * Every cell has ONE owning thread, which adds the cell's samples of this call in ascending s in registers and then adds
+ * the eight sums to `stats` once: no atomics, so the same calls in the same order give the same bits.  Cells of a group
+ * that does not occur in `group` are neither read nor written.
+ * Lanes run along the nodes.  An operand with stride_i == 1 (the dataset target, a baseline -- stride_h may be 0) is read
+ * in place; an operand with stride_h == 1 and stride_i == H (the model's permuted output view: 64 nodes x H horizons are
+ * 64*H contiguous floats) goes through a padded LDS tile when 1 < H <= TECM_MAP_LDS_MAX_H; every other stride
+ * combination, and larger H, is read in place with whatever coalescing its strides give.  All addressing is 64-bit.
+ * G and ceil(H / 4) must be <= 65535 (grid dimensions). */
+#define TECM_BAD_GROUP 16
+#define TECM_MAP_LDS_MAX_H 32
+typedef struct {
+  const float* pred; int64_t p_stride_s, p_stride_h, p_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  int64_t S; int32_t H; int32_t G; int64_t I;          /* samples, horizons, groups, nodes */
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  int32_t _pad2;
+  double* stats;
+  const int32_t* group;
+  int32_t* err_flag;
+} TecmMetricsMap;
+int tecm_metrics_map(const TecmMetricsMap* m, void* stream);
 
 /* (4) sliding-window batch assembly from device-resident series (SlidingWindowSamplerDataset.__getitem__
  * src/data/dataset.py:65-99 + the harness reshapes train.py:62-65, :76): for sample b with window

@@ -2,6 +2,7 @@
 // buffers (train.py:92-109, :358-366), evaluation statistics on device (src/evaluation/metrics.py),
 // sliding-window batch assembly (src/data/dataset.py:65-99).  All three are HBM-bound streaming kernels.
 #include "common.h"
+#include "metrics_value.h"
 
 namespace {
 
@@ -82,17 +83,7 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
 }
 
 // ------------------------------------------------------------------ evaluation statistics
-__device__ __forceinline__ float unscale_f32(float y, double mean, double scale) {
-  // sklearn StandardScaler.inverse_transform on a float32 array: X *= scale_ ; X += mean_ (two f32 roundings)
-  const float a = (float)((double)y * scale);
-  return (float)((double)a + mean);
-}
-__device__ __forceinline__ float nan_to_num_tec(float v) {
-  if (v != v) return 0.f;
-  if (isinf(v)) return v > 0.f ? 100.f : 0.f;
-  return v;
-}
-
+// unscale_f32, nan_to_num_tec: metrics_value.h (shared with metrics_map.hip)
 __global__ __launch_bounds__(256) void metrics_kernel(TecmMetrics q, int chunks) {
   __shared__ double red[4];
   const int h = blockIdx.y;

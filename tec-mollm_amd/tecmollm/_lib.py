@@ -12,7 +12,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TECM_LIB", os.path.join(_HERE, "libtecmollm_hip.so"))   # override for experiments
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 c_f32p = C.c_void_p
 
@@ -106,6 +106,17 @@ class TecmMetrics(C.Structure):
     ]
 
 
+class TecmMetricsMap(C.Structure):
+    _fields_ = [
+        ("pred", c_f32p), ("p_stride_s", C.c_int64), ("p_stride_h", C.c_int64), ("p_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("G", C.c_int32), ("I", C.c_int64),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("_pad2", C.c_int32),
+        ("stats", C.c_void_p), ("group", C.c_void_p), ("err_flag", C.c_void_p),
+    ]
+
+
 class TecmWindowBatch(C.Structure):
     _fields_ = [
         ("X", c_f32p), ("TF", c_f32p), ("Y", c_f32p), ("starts", C.c_void_p), ("starts_host_check", C.c_void_p),
@@ -156,6 +167,7 @@ class TecmConvFwd(C.Structure):
 
 TECM_NORM_BLOCKS = 512
 TECM_METRIC_STATS = 8
+TECM_MAP_LDS_MAX_H = 32
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
 
 
@@ -237,6 +249,7 @@ EXPORTS = {
     "tecm_checksum_verify": (C.c_int, [c_f32p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "tecm_seed_advance": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "tecm_metrics_accumulate": (C.c_int, [C.POINTER(TecmMetrics), C.c_void_p]),
+    "tecm_metrics_map": (C.c_int, [C.POINTER(TecmMetricsMap), C.c_void_p]),
     "tecm_window_batch": (C.c_int, [C.POINTER(TecmWindowBatch), C.c_void_p]),
     "tecm_window_baseline": (C.c_int, [C.POINTER(TecmWindowBaseline), C.c_void_p]),
     "tecm_slot_mean": (C.c_int, [C.POINTER(TecmSlotMean), C.c_void_p]),

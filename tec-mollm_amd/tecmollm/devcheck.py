@@ -12,7 +12,9 @@ synchronisation to the step:
     anything that already synchronises -- raises `IndexError` once that copy has landed and the word is non-zero;
     `poll(sync=True)` waits for the copy first.
 
-Bit 16 is used by the data-parallel rank-divergence check (tecmollm/train.py).
+Bit 4 (TECM_BAD_GROUP) is set by the per-cell evaluation statistics (`MapMetrics.update`) when a sample's group id lies
+outside [0, num_groups): the sample is skipped, and `poll()` raises `TecmError`.  Bit 16 is used by the data-parallel
+rank-divergence check (tecmollm/train.py).
 """
 from __future__ import annotations
 
@@ -20,11 +22,15 @@ from typing import Dict, Optional
 
 import torch
 
+from ._lib import TecmError
+
 BAD_TOD, BAD_DOY, BAD_YEAR, BAD_SEASON = 1, 2, 4, 8
+BAD_GROUP = 16
 RANKS_DIVERGED = 1 << 16
 
 _NAMES = {BAD_TOD: "time-of-day index outside [0, 12)", BAD_DOY: "day-of-year index outside [0, 366)",
           BAD_YEAR: "year index outside [0, num_years)", BAD_SEASON: "season index outside [0, 4)",
+          BAD_GROUP: "group id outside [0, num_groups) (the sample was skipped)",
           RANKS_DIVERGED: "data-parallel ranks no longer hold identical parameters"}
 
 
@@ -62,7 +68,9 @@ class DeviceErrorWord:
             self.host.zero_()
             self.event = None
             what = "; ".join(text for bit, text in _NAMES.items() if code & bit)
-            if code & RANKS_DIVERGED and not (code & 15):
+            if not (code & 15):
+                if code & BAD_GROUP:
+                    raise TecmError(f"device error word = {code:#x} (TECM_BAD_GROUP): {what}")
                 raise RuntimeError(f"device error word = {code:#x}: {what}")
             raise IndexError(f"index out of range in self (device error word = {code:#x}): {what} -- the reference's "
                              "nn.Embedding raises here (modules.py:255-258); every output built from the bad index is NaN")

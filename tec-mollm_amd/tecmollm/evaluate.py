@@ -8,6 +8,11 @@ and `get_baseline_predictions` keeps the reference's signature and returns the r
 the model and the baselines in ONE pass over the batches (`test.py:195-217` makes two passes and collects everything on
 the host), `improvement` is `test.py:243-251`, `write_report` is `test.py:260-276` without pandas.
 
+`evaluate_maps` is the same pass one level down: besides the per-horizon dicts it keeps every forecast's statistics per
+(group of the window, horizon, node) on the device (`MapMetrics`), for error maps and for scores stratified by storm level
+(`window_groups_by_index`) or time of day (`window_groups_by_slot`); `write_maps` writes them out.  The reference has no
+counterpart: its numbers pool every node and window.
+
 All three baselines take one channel of the FEATURE-scaled `X` as it is and are scored against the TARGET-scaled `Y`, as the
 reference's own baseline is (`test.py:59` against `:217`): the comparison a `test.py` user has been looking at stays the same.
 """
@@ -23,6 +28,7 @@ import torch
 
 from . import _lib
 from ._lib import TecmWindowBaseline, check, lib, stream_ptr
+from .devcheck import check_device_errors
 from .loop import _batches
 
 KINDS = {"mean": _lib.TECM_BASELINE_MEAN, "last": _lib.TECM_BASELINE_LAST, "periodic": _lib.TECM_BASELINE_PERIODIC}
@@ -87,6 +93,36 @@ def get_baseline_predictions(test_dataset, L_in: int, L_out: int) -> np.ndarray:
     return out.cpu().numpy()
 
 
+def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_weight, order, groups, num_groups):
+    """The one pass over the batches that `evaluate_split` and `evaluate_maps` share: every forecast feeds a `HorizonMetrics`
+    of its own and, when `num_groups` is given, a `MapMetrics` too.  Returns ({name: HorizonMetrics}, {name: MapMetrics})."""
+    from src.evaluation.metrics import HorizonMetrics, MapMetrics
+    kinds = list(baselines)
+    for k in kinds:
+        if k not in KINDS:
+            raise ValueError(f"baselines must come from {sorted(KINDS)}, got {k!r}")
+    model.eval()
+    hms: Dict[str, HorizonMetrics] = {}
+    mms: Dict[str, MapMetrics] = {}
+    for chunk in _batches(len(dataset), batch_size, order):
+        x, tf, y = dataset.batch(chunk)
+        out = model(x, tf, edge_index, edge_weight)
+        if not hms:
+            for name in [MODEL_NAME] + [NAMES[k] for k in kinds]:
+                hms[name] = HorizonMetrics(out.shape[1], scaler, device=out.device)
+                if num_groups is not None:
+                    mms[name] = MapMetrics(out.shape[1], out.shape[2], num_groups, scaler, device=out.device)
+        ids = None
+        if mms and groups is not None:
+            ids = groups[torch.as_tensor(chunk, dtype=torch.int64).to(groups.device, non_blocking=True)]
+        forecasts = [(MODEL_NAME, out)] + [(NAMES[k], window_baseline(dataset, chunk, k)) for k in kinds]
+        for name, pred in forecasts:
+            hms[name].update(pred, y)
+            if mms:
+                mms[name].update(pred, y, ids)
+    return hms, mms
+
+
 @torch.no_grad()
 def evaluate_split(model: torch.nn.Module, dataset, edge_index: torch.Tensor, batch_size: int, scaler=None,
                    baselines: Sequence[str] = ("mean",), edge_weight: Optional[torch.Tensor] = None,
@@ -97,25 +133,86 @@ def evaluate_split(model: torch.nn.Module, dataset, edge_index: torch.Tensor, ba
     One pass over the batches: the model's output and each baseline's stride-0 view are fed in place to a
     `HorizonMetrics` of their own, with no host synchronisation per batch.  `order` and `group` as in `loop.validate`:
     a rank evaluates its shard and every rank returns the metrics of the whole split."""
-    from src.evaluation.metrics import HorizonMetrics
-    kinds = list(baselines)
-    for k in kinds:
-        if k not in KINDS:
-            raise ValueError(f"baselines must come from {sorted(KINDS)}, got {k!r}")
-    model.eval()
-    hms: Dict[str, HorizonMetrics] = {}
-    for chunk in _batches(len(dataset), batch_size, order):
-        x, tf, y = dataset.batch(chunk)
-        out = model(x, tf, edge_index, edge_weight)
-        if not hms:
-            for name in [MODEL_NAME] + [NAMES[k] for k in kinds]:
-                hms[name] = HorizonMetrics(out.shape[1], scaler, device=out.device)
-        hms[MODEL_NAME].update(out, y)
-        for k in kinds:
-            hms[NAMES[k]].update(window_baseline(dataset, chunk, k), y)
+    hms, _ = _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_weight, order, None, None)
     if not hms:
         raise ValueError("evaluate_split() on an empty dataset")
     return {name: hm.merge_(group).compute() for name, hm in hms.items()}
+
+
+@torch.no_grad()
+def evaluate_maps(model: torch.nn.Module, dataset, edge_index: torch.Tensor, batch_size: int, scaler=None,
+                  baselines: Sequence[str] = ("mean",), groups: Optional[torch.Tensor] = None, num_groups: int = 1,
+                  edge_weight: Optional[torch.Tensor] = None, order: Optional[Sequence[int]] = None, group=None):
+    """`evaluate_split` plus, per forecast, its errors per (group, horizon, node): returns (results, maps) with `results`
+    exactly what `evaluate_split` returns and `maps[name]` that forecast's `MapMetrics.compute()` -- (G, H, N) arrays
+    of count / mae / rmse / bias / r2_score / pearson_r and the pooled dict of every group.
+
+    `groups` holds one int32 id in [0, num_groups) per DATASET index, on the device (`window_groups_by_index`,
+    `window_groups_by_slot`); None puts every window in group 0.  The same single pass as `evaluate_split`; an id outside
+    its range is skipped by the kernel and raises here.  `order` and `group` as in `evaluate_split`."""
+    if groups is not None and (groups.dtype != torch.int32 or groups.shape != (len(dataset),)):
+        raise ValueError(f"groups must be an int32 tensor with one id per dataset index ({len(dataset)})")
+    hms, mms = _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_weight, order, groups,
+                           int(num_groups))
+    if not hms:
+        raise ValueError("evaluate_maps() on an empty dataset")
+    results = {name: hm.merge_(group).compute() for name, hm in hms.items()}
+    maps = {name: mm.merge_(group).compute() for name, mm in mms.items()}
+    check_device_errors(next(iter(mms.values())).stats.device)
+    return results, maps
+
+
+def _window_groups(series: torch.Tensor, starts: torch.Tensor, L_in: int, L_out: int, edges, span: str, reduce: str,
+                   mean: float = 0.0, scale: float = 1.0) -> torch.Tensor:
+    """(T,) series, (S,) int64 window starts -> (S,) int32 bucket of the series reduced over every window's span."""
+    if span not in ("input", "target"):
+        raise ValueError(f"span must be 'input' or 'target', got {span!r}")
+    if reduce not in ("max", "min", "last"):
+        raise ValueError(f"reduce must be 'max', 'min' or 'last', got {reduce!r}")
+    first, length = (starts, L_in) if span == "input" else (starts + L_in, L_out)
+    series = series.to(torch.float64) * scale + mean
+    if reduce == "last":
+        value = series[first + length - 1]
+    else:
+        windows = series.unfold(0, length, 1)                              # (T - length + 1, length) view
+        value = (windows.max(dim=1).values if reduce == "max" else windows.min(dim=1).values)[first]
+    bounds = torch.as_tensor(edges, dtype=torch.float64, device=series.device).reshape(-1)
+    if bounds.numel() > 1 and not bool((bounds[1:] >= bounds[:-1]).all()):
+        raise ValueError("edges must be ascending")
+    return torch.bucketize(value, bounds).to(torch.int32)
+
+
+def _feature_scale(feature_scaler, channel: int):
+    if feature_scaler is None:
+        return 0.0, 1.0
+    if isinstance(feature_scaler, (tuple, list)):
+        return float(feature_scaler[0]), float(feature_scaler[1])
+    return float(np.asarray(feature_scaler.mean_).reshape(-1)[channel]), float(np.asarray(feature_scaler.scale_).reshape(-1)[channel])
+
+
+def window_groups_by_index(dataset, channel: int, edges, span: str = "target", feature_scaler=None,
+                           reduce: str = "max") -> torch.Tensor:
+    """One int32 group id per dataset index, on the device, from a space-weather index: channels 1-5 of `X` (AE, Dst,
+    F10.7, Kp, ap) hold one value per time step, broadcast over the grid (feature_engineering.py:27-36), so the series
+    is read at node 0.  It is reduced (`max`, `min` or `last`) over the window's L_in input steps (span "input") or its
+    L_out target steps (span "target") and bucketed with `edges` as `torch.bucketize` does: id = number of edges below
+    the value, a value equal to an edge falls in the lower group; len(edges) + 1 groups.  `feature_scaler` (a fitted
+    StandardScaler over X's channels, or a (mean, scale) pair for this channel) undoes the feature scaling first, so that
+    `edges` are in the index's own units: Kp bins, Dst thresholds."""
+    T, H, W, Cc = dataset.X.shape
+    if not 0 <= int(channel) < Cc:
+        raise ValueError(f"channel {channel} outside [0, {Cc})")
+    mean, scale = _feature_scale(feature_scaler, int(channel))
+    starts = torch.tensor(dataset.sample_indices, dtype=torch.int64).to(dataset.X.device)
+    return _window_groups(dataset.X[:, 0, 0, int(channel)], starts, dataset.L_in, dataset.L_out, edges, span, reduce,
+                          mean, scale)
+
+
+def window_groups_by_slot(dataset) -> torch.Tensor:
+    """The time-of-day slot, 0..11, of every window's first target step (column 0 of the time features), int32 on the
+    device: the grouping of a day / night table."""
+    starts = torch.tensor(dataset.sample_indices, dtype=torch.int64).to(dataset.X.device)
+    return dataset.time_features[starts + dataset.L_in, 0].to(torch.int32)
 
 
 def improvement(results: Dict[str, Dict[str, object]], model: str = MODEL_NAME,
@@ -164,3 +261,33 @@ def write_report(results: Dict[str, Dict[str, object]], output_dir: str) -> Dict
             f.write(f"  mean R2:   {metrics['r2_score_avg']:.6f}\n")
             f.write(f"  mean Pearson R: {metrics['pearson_r_avg']:.6f}\n\n")
     return {"csv": csv_path, "summary": txt_path}
+
+
+def write_maps(maps: Dict[str, Dict[str, object]], output_dir: str, grid: Optional[Sequence[int]] = None) -> Dict[str, str]:
+    """The files of `evaluate_maps`' second result: `error_maps.npz` with one array `<forecast>/<metric>` of shape (G, H, N)
+    per forecast and metric -- (G, H, *grid) when `grid`, e.g. (41, 71), is given -- and `evaluation_by_group.csv` with one
+    row per forecast and group: the number of (window, node) pairs and the four averages of that group's pooled dict.
+    numpy and the standard library only.  Returns the two paths."""
+    from src.evaluation.metrics import MAP_KEYS
+    os.makedirs(output_dir, exist_ok=True)
+    arrays = {}
+    for name, m in maps.items():
+        for k in MAP_KEYS:
+            a = np.asarray(m[k])
+            if grid is not None:
+                if int(np.prod(grid)) != a.shape[2]:
+                    raise ValueError(f"grid {tuple(grid)} does not hold {a.shape[2]} nodes")
+                a = a.reshape(a.shape[0], a.shape[1], *[int(d) for d in grid])
+            arrays[f"{name}/{k}"] = a
+    npz_path = os.path.join(output_dir, "error_maps.npz")
+    np.savez_compressed(npz_path, **arrays)
+    csv_path = os.path.join(output_dir, "evaluation_by_group.csv")
+    cols = ("mae_avg", "rmse_avg", "r2_score_avg", "pearson_r_avg")
+    with open(csv_path, "w", newline="", encoding="utf-8") as f:
+        wr = csv.writer(f)
+        wr.writerow(["forecast", "group", "count"] + list(cols))
+        for name, m in maps.items():
+            count = np.asarray(m["count"])
+            for g, pooled in enumerate(m["by_group"]):
+                wr.writerow([name, g, int(count[g, 0].sum())] + [repr(float(pooled[k])) for k in cols])
+    return {"npz": npz_path, "csv": csv_path}

@@ -78,9 +78,15 @@ enum { TECM_ACT_NONE = 0, TECM_ACT_GELU_ERF = 1, TECM_ACT_GELU_TANH = 2 };
  * modules.py:208), peft LoRA A/B (modules.py:177-186), GATv2 is NOT here (tecm_spatial_*), and
  * their autograd backward (dX and dW forms).
  * Epilogue order: v = alpha*acc; v += bias[n]; v += rowbias[((m / rb_div) % rb_mod)*rb_ld + n];
- *   if preact: preact[m*ldp+n] = v;  v = act(v);  if dact_src: v *= act'(dact_src[m*ldd+n]);
- *   v = dropout(v, out_drop);  if residual: v += residual[m*ldr+n];  if accumulate: v += C[m,n];
- *   store C (through c_win when enabled: column n is the inner index kk of the view). */
+ *   if preact: preact[m*ldp+n] = v   (a bf16 preact stores bf16(v) and continues with v = float(bf16(v)));
+ *   if dact_src: v *= act'(dact_src[m*ldd+n])   else: v = act(v)      -- one or the other, never both: with dact_src,
+ *     `act` only names the activation whose derivative is taken and must not be TECM_ACT_NONE (TECM_E_ARG);
+ *   v = dropout(v, out_drop): mask index row*out_drop.ld + col of the element of C being stored (under c_win the
+ *     target row and column of the view);
+ *   if residual: v += residual[m*ldr+n];  if accumulate: v += the previous value of the element of C being stored;
+ *   store C (through c_win when enabled: column n is the inner index kk of the view; an element whose t_in falls
+ *   outside [0, Lin) is dropped).  split_k > 1 applies the same epilogue to the reduced sum.
+ * tests/gemm_epilogue_ref.py states this order in fp64; tests/test_gpu_gemm_epilogue.py holds every kernel family to it. */
 /* io_bf16 (tecm_gemm_bf16 only, 0 everywhere else): which tensors of the call already are / shall be bf16 in HBM.
  * A bf16 operand is [row][k] with k contiguous and its leading dimension counted in bf16 elements (multiple of 8,
  * 16-byte aligned, K % 8 == 0); the call must be the plain MK x NK contraction.  TECM_IO_C_BF16 writes C as bf16

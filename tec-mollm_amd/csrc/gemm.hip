@@ -119,6 +119,8 @@ static int gemm_entry(const TecmGemm* d, void* stream, int mode) {
   TECM_REQUIRE(!(g.c_win.enabled && (int64_t)g.c_win.taps * g.c_win.Cw != g.N), TECM_E_ARG,
                "tecm_gemm_f32: c_win taps*Cw != N");
   TECM_REQUIRE(!(g.rowbias && (g.rb_div <= 0 || g.rb_mod <= 0)), TECM_E_ARG, "tecm_gemm_f32: bad rowbias spec");
+  TECM_REQUIRE(!(g.dact_src && g.act == TECM_ACT_NONE), TECM_E_ARG,
+               "tecm_gemm_f32: dact_src needs act to name the activation whose derivative is taken");
   TECM_REQUIRE(!(g.split_k > 1 && g.workspace == nullptr), TECM_E_ARG, "tecm_gemm_f32: split_k needs a workspace");
   TECM_REQUIRE(g.a_layout == TECM_A_MK || g.b_layout == TECM_B_KN, TECM_E_ARG,
                "tecm_gemm_f32: layout combination KM x NK is not built");

@@ -62,6 +62,8 @@ def gemm(M: int, N: int, K: int, A: torch.Tensor, lda: int, B: torch.Tensor, ldb
     # bf16 (activations rounded once by their producer, cached bf16 weights) and / or a bf16 output for such a consumer
     """C[M,N] = epilogue(alpha * A_view[M,K] . B_view[K,N]); see TecmGemm in include/tecmollm.h.
     *_off are element offsets added to the base pointers (column slices of wider buffers).
+    dact_src replaces the activation by a multiplication with act'(dact_src); act then names the activation whose
+    derivative is taken and must not be ACT_NONE (the library refuses it).
     bf16 is the precision code: 0/False exact fp32, 1/True bf16 matrix cores, 2 bf16x3 (split-bf16, ~1e-5),
     3 bf16x6 (three-way split, fp32-grade).
     bf16=True asks for the bf16 matrix cores (operands rounded to bf16, fp32 accumulate); calls the bf16

@@ -231,6 +231,27 @@ int tecm_spatial_bwd_blocks(const TecmSpatial* d);
 int64_t tecm_spatial_fwd_lds_bytes(int32_t win_max, int32_t tile_nodes, int32_t tile_edges_max);
 int64_t tecm_spatial_bwd_lds_bytes(int32_t win_max, int32_t tile_nodes, int32_t tile_edges_max, int32_t Demb);
 
+/* Gradient of the fused stage (flags == 0, Cin 6 or 10) with respect to its input x (csrc/spatial_dx.hip):
+ *   dx_n = dout_n[:Cin] + W_l[:, :Cin]^T d x_l[n] + W_r[:, :Cin]^T d x_r[n]
+ * for the same descriptor the forward ran with (alpha_drop included: the masks are recomputed).  No float atomics: dx is
+ * bit-reproducible.  Any graph the forward accepts is served, with block-uniform or per-node time features; the tiling
+ * fields of `d` are checked but not used.  A time index outside its table gives NaN rows of dx and sets *err_flag. */
+typedef struct TecmSpatialDx {
+  const float* dout;                      /* (B, L, N, 24): the padded rows the fused stage writes, 16-byte aligned */
+  float* dx; int64_t dx_ld;               /* (B*L*N, dx_ld >= Cin): columns [0, Cin) of every row are written */
+  float* ws;                              /* tecm_spatial_dx_ws_floats(d) floats, 16-byte aligned; contents undefined after */
+  /* the whole graph's non-self edges grouped by SOURCE: entries src_rowptr[j] .. src_rowptr[j + 1] leave node j; entry q
+   * goes to target src_target[q] and is slot src_slot[q] of that target's list in the by-target CSR
+   * (colidx[rowptr[target] + slot] == j), which makes its dropout index the forward's. */
+  const int32_t* src_rowptr;              /* (N+1) */
+  const int32_t* src_target;              /* (E) */
+  const int32_t* src_slot;                /* (E) */
+} TecmSpatialDx;
+/* Floats of workspace the call needs (x_l, x_r and three softmax statistics per (row, head) for one chunk of graphs, at most
+ * 64 MiB unless a single graph needs more), or 0 when `d` is not served.  Pure host function. */
+int64_t tecm_spatial_dx_ws_floats(const TecmSpatial* d);
+int tecm_spatial_dx(const TecmSpatial* d, const TecmSpatialDx* g, void* stream);
+
 /* ------------------------------------------------------------------ stage a-4 normalisation
  * nn.GroupNorm(1, C) + nn.GELU() (modules.py:28-29) for the three parallel branches at once.
  * y/act: (B, L, N, CT) time-major with CT = 3*Cout (branch j owns channels [j*Cout,(j+1)*Cout)).

@@ -1,8 +1,8 @@
 // Backward of the fused stage a-1..a-3, second formulation (round 5; the forward: spatial_fwd2.hip; reference
 // SpatioTemporalEmbedding modules.py:230-266 + GATv2Conv modules.py:329-336, :356 + residual tec_mollm.py:94).  Nothing
-// was saved by the forward: x_l / x_r are recomputed, and the kernel reduces straight to PARAMETER gradients -- x needs
-// none.  Served: the configuration TEC_MoLLM.forward runs (block-uniform time features, flags = 0, 24-float rows);
-// everything else stays on spatial_bwd.hip.
+// was saved by the forward: x_l / x_r are recomputed, and the kernel reduces straight to PARAMETER gradients -- the
+// gradient of x, where a caller asks for it, is a launch of its own (spatial_dx.hip).  Served: the configuration
+// TEC_MoLLM.forward runs (block-uniform time features, flags = 0, 24-float rows); everything else stays on spatial_bwd.hip.
 //
 // Against the first formulation (one persistent 512-thread block per CU, 146 KiB of LDS, every phase latency-bound):
 //   * a block is (tile of <= 128 targets, chunk of graphs): 256 threads, ~45 KiB of LDS -> three blocks per CU;

@@ -2,11 +2,14 @@
 
 Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
   csrc/            hand-written HIP kernels + the C ABI (include/tecmollm.h at the repo root)
-  tecmollm/        ctypes binding, autograd stage functions, graph preparation, training-step helpers, test-split evaluation
+  tecmollm/        ctypes binding, autograd stage functions, graph preparation, training-step helpers, test-split evaluation,
+                   input attribution
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/models/      mirror of the reference's baselines (`from src.models.baselines import HistoricalAverage`)
 """
 from ._lib import LIB_PATH, TecmError, lib  # noqa: F401
 from .devcheck import check_device_errors  # noqa: F401
+from .attribute import attribution_maps, input_gradient, integrated_gradients, write_attributions  # noqa: F401
 
-__all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors"]
+__all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradient", "integrated_gradients",
+           "attribution_maps", "write_attributions"]

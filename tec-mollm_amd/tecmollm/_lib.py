@@ -76,6 +76,13 @@ class TecmSpatialGrads(C.Structure):
     ]
 
 
+class TecmSpatialDx(C.Structure):
+    _fields_ = [
+        ("dout", c_f32p), ("dx", c_f32p), ("dx_ld", C.c_int64), ("ws", c_f32p),
+        ("src_rowptr", C.c_void_p), ("src_target", C.c_void_p), ("src_slot", C.c_void_p),
+    ]
+
+
 class TecmLnAdd(C.Structure):
     _fields_ = [("dy2", C.c_void_p), ("ld", C.c_int64), ("bf16", C.c_int32), ("_pad", C.c_int32), ("drop", TecmDrop)]
 
@@ -188,6 +195,8 @@ EXPORTS = {
     "tecm_spatial_bwd_blocks": (C.c_int, [C.POINTER(TecmSpatial)]),
     "tecm_spatial_bwd2_blocks": (C.c_int, [C.POINTER(TecmSpatial)]),
     "tecm_spatial_bwd2": (C.c_int, [C.POINTER(TecmSpatial), C.POINTER(TecmSpatialGrads), c_f32p, C.c_void_p]),
+    "tecm_spatial_dx_ws_floats": (C.c_int64, [C.POINTER(TecmSpatial)]),
+    "tecm_spatial_dx": (C.c_int, [C.POINTER(TecmSpatial), C.POINTER(TecmSpatialDx), C.c_void_p]),
     "tecm_groupnorm_gelu_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
     "tecm_gn_y16_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),

@@ -263,6 +263,12 @@ def write_report(results: Dict[str, Dict[str, object]], output_dir: str) -> Dict
     return {"csv": csv_path, "summary": txt_path}
 
 
+def check_grid(grid: Sequence[int], num_nodes: int) -> None:
+    """Raises ValueError unless the (rows, columns) `grid` holds exactly `num_nodes` nodes."""
+    if int(np.prod(grid)) != num_nodes:
+        raise ValueError(f"grid {tuple(grid)} does not hold {num_nodes} nodes")
+
+
 def write_maps(maps: Dict[str, Dict[str, object]], output_dir: str, grid: Optional[Sequence[int]] = None) -> Dict[str, str]:
     """The files of `evaluate_maps`' second result: `error_maps.npz` with one array `<forecast>/<metric>` of shape (G, H, N)
     per forecast and metric -- (G, H, *grid) when `grid`, e.g. (41, 71), is given -- and `evaluation_by_group.csv` with one
@@ -275,8 +281,7 @@ def write_maps(maps: Dict[str, Dict[str, object]], output_dir: str, grid: Option
         for k in MAP_KEYS:
             a = np.asarray(m[k])
             if grid is not None:
-                if int(np.prod(grid)) != a.shape[2]:
-                    raise ValueError(f"grid {tuple(grid)} does not hold {a.shape[2]} nodes")
+                check_grid(grid, a.shape[2])
                 a = a.reshape(a.shape[0], a.shape[1], *[int(d) for d in grid])
             arrays[f"{name}/{k}"] = a
     npz_path = os.path.join(output_dir, "error_maps.npz")

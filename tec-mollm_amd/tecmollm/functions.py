@@ -17,7 +17,7 @@ from typing import List, Optional
 import torch
 
 from . import devcheck, ops
-from ._lib import TecmSpatial, TecmSpatialGrads, check, lib, stream_ptr
+from ._lib import TecmSpatial, TecmSpatialDx, TecmSpatialGrads, check, lib, stream_ptr
 from .graph import GraphMeta
 from .ops import (A_KM, A_MK, ACT_GELU_ERF, ACT_GELU_TANH, B_KN, B_NK, colsum, drop, gemm, pick_split_k, win)
 
@@ -160,6 +160,9 @@ class SpatialFn(torch.autograd.Function):
         dout = dout.contiguous()
         d = SpatialFn._desc(x, tf, node_tab, tod_tab, doy_tab, year_tab, season_tab, Wl, bl, Wr, br, att, bias, meta,
                             ctx.heads, ctx.R, ctx.plan, B, L, N, Cin, Demb)
+        dx = SpatialFn._input_grad(d, dout, x, meta) if ctx.needs_input_grad[0] else None
+        if not any(ctx.needs_input_grad[2:13]):               # frozen parameters (attribution): no parameter launch, no column sums
+            return (dx,) + (None,) * 16
         # round 5: the second formulation (csrc/spatial_bwd2.hip) wherever it serves the call; TECM_SPATIAL_V2=0 / TECM_SPATIAL_BWD2=0
         # keep the persistent kernel (A/B)
         v2 = os.environ.get("TECM_SPATIAL_V2", "1")[:1] != "0" and os.environ.get("TECM_SPATIAL_BWD2", "1")[:1] != "0"
@@ -198,8 +201,27 @@ class SpatialFn(torch.autograd.Function):
         datt = s[o:o + Cc].view_as(att)
         dbias = colsum(dout, CP, B * L * N, 1, 1, CP)[0, :Cc]   # d bias = column sums of dout (out = h + gat + bias);
         #                                                         all 24 padded columns: the float4 reduction path
-        return (None, None, d_node, d_tod, d_doy, d_year, d_season, dWl, dbl, dWr, dbr, datt, dbias,
+        return (dx, None, d_node, d_tod, d_doy, d_year, d_season, dWl, dbl, dWr, dbr, datt, dbias,
                 None, None, None, None)
+
+    @staticmethod
+    def _input_grad(d: TecmSpatial, dout, x, meta: GraphMeta):
+        """d x (B, L, N, Cin) through GATv2, the residual and the embedding concat (csrc/spatial_dx.hip): no float atomics,
+        bit-reproducible."""
+        nws = lib().tecm_spatial_dx_ws_floats(C.byref(d))
+        if nws <= 0:
+            raise _lib_error("SpatialFn: the input gradient serves Cin 6 or 10 with d_emb = 22 - Cin "
+                             f"(got Cin = {x.shape[-1]})")
+        dx = torch.empty_like(x)
+        ws = torch.empty(nws, device=x.device, dtype=torch.float32)
+        g = TecmSpatialDx()
+        g.dout, g.dx, g.dx_ld, g.ws = dout.data_ptr(), dx.data_ptr(), x.shape[-1], ws.data_ptr()
+        g.src_rowptr, g.src_target = meta.out_ptr.data_ptr(), meta.out_target.data_ptr()
+        g.src_slot = meta.out_slot.data_ptr()
+        errs = devcheck.error_word(x.device)
+        check(lib().tecm_spatial_dx(C.byref(d), C.byref(g), stream_ptr()), "tecm_spatial_dx")
+        errs.post()
+        return dx
 
 
 class EmbedFn(torch.autograd.Function):
@@ -259,7 +281,8 @@ class EmbedFn(torch.autograd.Function):
 class GatFn(torch.autograd.Function):
     """Stand-alone SpatialEncoder.forward (modules.py:340-359): x (G, N, 22) -> GATv2Conv(x) (G, N, 22), no residual,
     no embedding: the fused kernels with Demb = 0 (the input rows ARE h) and TECM_SPATIAL_NO_RESIDUAL.  Gradients for
-    the GATv2 parameters; the input itself gets none (the fused path never needs d x), so x must not require grad."""
+    the GATv2 parameters; the input itself gets none, so x must not require grad: the input gradient (csrc/spatial_dx.hip)
+    is built for the fused stage, where TEC_MoLLM.forward needs it, and backward refuses here rather than return nothing."""
 
     @staticmethod
     def forward(ctx, x, Wl, bl, Wr, br, att, bias, meta: GraphMeta, heads: int, graphs_with_edges: int, plan: DropPlan):

@@ -36,6 +36,10 @@ class GraphMeta:
     src_ptr: torch.Tensor      # int32: per tile, W+1 offsets into the tile's edge segment, grouped by source row
     src_col: torch.Tensor      # int32 (E'): ((target - n0) << 16) | slot, tile segments aligned with colidx
     src_ptr_off: torch.Tensor  # int32 (num_tiles): start of each tile's src_ptr run
+    # the whole graph by source (the input gradient, csrc/spatial_dx.hip): entries out_ptr[j] .. out_ptr[j + 1] leave node j
+    out_ptr: torch.Tensor      # int32 (N+1)
+    out_target: torch.Tensor   # int32 (E'): target of the entry
+    out_slot: torch.Tensor     # int32 (E'): its position in the target's list: colidx[rowptr[target] + slot] == j
 
 
 def csr_by_target(edge_index: np.ndarray, num_nodes: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -91,6 +95,19 @@ def by_source_lists(rowptr: np.ndarray, colidx: np.ndarray, num_nodes: int, tile
     return np.concatenate(ptrs), src_col, np.asarray(offs, dtype=np.int32)
 
 
+def csr_by_source(rowptr: np.ndarray, colidx: np.ndarray, num_nodes: int):
+    """The by-target CSR regrouped by SOURCE over the whole graph: (out_ptr (N+1), out_target (E'), out_slot (E')).  The
+    entries of a source keep the order of their targets, and every entry carries the slot it has in its target's list, so
+    that a sweep by source finds the forward's dropout index ((row*H + head)*ld + slot)."""
+    deg = np.diff(rowptr).astype(np.int64)
+    tgt = np.repeat(np.arange(num_nodes, dtype=np.int64), deg)           # target of every by-target entry
+    slot = np.arange(colidx.size, dtype=np.int64) - np.repeat(rowptr[:-1].astype(np.int64), deg)
+    order = np.argsort(colidx, kind="stable")
+    out_ptr = np.zeros(num_nodes + 1, dtype=np.int64)
+    np.add.at(out_ptr, colidx.astype(np.int64) + 1, 1)
+    return np.cumsum(out_ptr).astype(np.int32), tgt[order].astype(np.int32), slot[order].astype(np.int32)
+
+
 MAX_WINDOW = 512    # the backward's by-source pass: two rounds of 256 rows
 
 
@@ -135,11 +152,14 @@ def build(edge_index: torch.Tensor, num_nodes: int, device: torch.device, demb: 
     tn, lo, hi, wmax, emax = chosen
     to = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)   # noqa: E731
     sp, sc, so = by_source_lists(rowptr, colidx, num_nodes, tn, lo, hi)
+    op, ot, os_ = csr_by_source(rowptr, colidx, num_nodes)
+    some = lambda a: a if a.size else np.zeros(1, np.int32)               # noqa: E731  (never a null device pointer)
     return GraphMeta(num_nodes=num_nodes, num_edges=int(colidx.size), max_deg=int(deg.max()) if deg.size else 0,
                      tile_nodes=tn, num_tiles=int(lo.size), win_max=wmax, tile_edges_max=emax,
                      rowptr=to(rowptr),
                      colidx=to(colidx if colidx.size else np.zeros(1, np.int32)), tile_lo=to(lo), tile_hi=to(hi),
-                     src_ptr=to(sp), src_col=to(sc), src_ptr_off=to(so))
+                     src_ptr=to(sp), src_col=to(sc), src_ptr_off=to(so),
+                     out_ptr=to(op), out_target=to(some(ot)), out_slot=to(some(os_)))
 
 
 _cache: Dict[Tuple[int, int, int, str], Tuple[torch.Tensor, GraphMeta]] = {}

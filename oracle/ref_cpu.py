@@ -97,16 +97,16 @@ def gatv2_conv(x: torch.Tensor, edge_index: torch.Tensor, p: Params, heads: int,
     dst = torch.cat([dst[keep], loops])
     s = xl[src] + xr[dst]                                    # (E',H,Ch)
     e = (F.leaky_relu(s, GAT_NEG_SLOPE) * att.view(1, H, Ch)).sum(-1)   # (E',H)
-    emax = torch.full((M, H), float("-inf")).scatter_reduce(
+    emax = torch.full((M, H), float("-inf"), dtype=e.dtype).scatter_reduce(
         0, dst.view(-1, 1).expand(-1, H), e, reduce="amax", include_self=True)
     pexp = (e - emax[dst]).exp()
-    denom = torch.zeros(M, H).index_add_(0, dst, pexp) + 1e-16
+    denom = torch.zeros(M, H, dtype=pexp.dtype).index_add_(0, dst, pexp) + 1e-16
     alpha = pexp / denom[dst]
     if alpha_keep is not None:
         alpha = alpha * alpha_keep / (1.0 - drop_p)
     if alpha_mult is not None:
         alpha = alpha * alpha_mult
-    out = torch.zeros(M, H, Ch).index_add_(0, dst, alpha.unsqueeze(-1) * xl[src])
+    out = torch.zeros(M, H, Ch, dtype=xl.dtype).index_add_(0, dst, alpha.unsqueeze(-1) * xl[src])
     return out.reshape(M, H * Ch) + bias
 
 

@@ -535,6 +535,23 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
       const int64_t rowi = (int64_t)(it.t * d.B + it.b) * N + i;            // row in the reference's (L*B*N) flattening
       const uint64_t dbase = (uint64_t)((rowi * H + hh) * d.alpha_drop.ld);
       const float base = (0.6f * LOG2E) * xr[CH];
+      // de = alpha (dalpha - sum alpha dalpha) does not change when every dalpha of the target is shifted by one constant.
+      // The self loop's dalpha (before dropout) is taken off: every rounding in sum alpha dalpha and in the products is
+      // relative to |dalpha|, and with a large component common to all sources (biases, an offset in x) |dalpha| is far
+      // above its spread over the sources.  The lin_r and att gradients sum de over a target's sources, where it cancels,
+      // and were left with that error (tests/test_host_hard_inputs.py restates both forms in plain fp32).
+      float da_ref;
+      {
+        float a[CH + 1];
+        load12(smem + m.xl + wi * CP + hh * 12, a);
+        float da = 0.f, db = 0.f;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          if (c & 1) db = fmaf(gv[c], a[c], db);
+          else da = fmaf(gv[c], a[c], da);
+        }
+        da_ref = da + db;
+      }
       // sweep 1: logits, dalpha, online softmax statistics over this lane's slots (slot deg = the implicit self loop)
       float mx = -INFINITY, z = 0.f, num = 0.f;
       for (int s = sub; s <= deg; s += 2) {
@@ -557,6 +574,7 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
         const float e = fmaf(0.4f * LOG2E, t0 + u0, fmaf(0.6f * LOG2E, a[CH], base));
         da += db;
         if (dth) da *= tecm_drop_mult(dseed, dbase + s, dth, dinv);
+        da -= da_ref;
         *reinterpret_cast<float2*>(smem + m.ea + (pos * 2 + hh) * 2) = make_float2(e, da);
         const float mn = fmaxf(mx, e);
         const float corr = __builtin_amdgcn_exp2f(mx - mn), pw = __builtin_amdgcn_exp2f(e - mn);
@@ -577,7 +595,7 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
         const int j = s < deg ? ecol[e0 + s] : wi;
         const int pos = s < deg ? e0 + s : E + tn;
         float2* slot = reinterpret_cast<float2*>(smem + m.ea + (pos * 2 + hh) * 2);
-        const float2 ed = *slot;                             // (e, dalpha * mult)
+        const float2 ed = *slot;                             // (e, dalpha * mult - da_ref)
         float a[CH + 1];
         load12(smem + m.xl + j * CP + hh * 12, a);
         const float alpha = __builtin_amdgcn_exp2f(ed.x - mm) * zinv;

@@ -217,6 +217,20 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
       const int64_t rowi = (int64_t)(t * d.B + b) * N + i;   // row in the reference's (L*B*N) flattening
       const uint64_t dbase = (uint64_t)((rowi * H + hh) * d.alpha_drop.ld);
       const float base = (0.6f * LOG2E) * xr[CH];
+      // every dalpha of the target is shifted by the self loop's (csrc/spatial_bwd.hip, B1: de does not change, and its
+      // roundings are relative to the spread of dalpha over the sources, not to a component common to all of them)
+      float da_ref;
+      {
+        float al[CH + 1];
+        ld12(R1 + wi * CP + hh * 12, al);
+        float da = 0.f, db = 0.f;
+#pragma unroll
+        for (int c = 0; c < CH; ++c) {
+          if (c & 1) db = fmaf(gvv[c], al[c], db);
+          else da = fmaf(gvv[c], al[c], da);
+        }
+        da_ref = da + db;
+      }
       // sweep 1: logits, dalpha, online softmax statistics (slot deg = the implicit self loop), three slots per step: the
       // LDS round trips of a step overlap (col -> x_l row -> arithmetic is a dependent chain per slot)
       constexpr int BU = 1;                                // (three slots per step measured slower: 745 vs 696 us -- 21 more spilled registers)
@@ -245,6 +259,7 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
           const float e = fmaf(0.4f * LOG2E, t0 + u0, fmaf(0.6f * LOG2E, al[CH], base));
           da += db;
           if (dth) da *= tecm_drop_mult(dseed, dbase + sl, dth, dinv);
+          da -= da_ref;
           if (valid) *reinterpret_cast<float2*>(R2 + (pos * 2 + hh) * 2) = make_float2(e, da);
           ev[u] = valid ? e : -INFINITY;
           dav[u] = valid ? da : 0.f;
@@ -275,7 +290,7 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
           const int j = sl < deg ? col[sl] : wi;
           const int pos = sl < deg ? e0 + sl : E + tn;
           float2* slot = reinterpret_cast<float2*>(R2 + (pos * 2 + hh) * 2);
-          const float2 ed = *slot;                           // (e, dalpha * mult)
+          const float2 ed = *slot;                           // (e, dalpha * mult - da_ref)
           float al[CH + 1];
           ld12(R1 + j * CP + hh * 12, al);
           const float alpha = __builtin_amdgcn_exp2f(ed.x - mx) * zinv;

@@ -608,6 +608,48 @@ typedef struct {
 } TecmMetricsMap;
 int tecm_metrics_map(const TecmMetricsMap* m, void* stream);
 
+/* (3c) probabilistic scores of a K-member ensemble per cell (g, h, i): every member and the target go through the value
+ * pipeline of (3) / (3b) (non-finite scaled member -> 0, inverse transform with two f32 roundings, nan_to_num, optional clip
+ * of the members only), which leaves float32 x_1..x_K and y; everything after that is float64.  With x_(1) <= ... <= x_(K)
+ * the sorted members, every sum over members taken in ascending sorted order, and m = trim, per (sample, horizon, node):
+ *   mu    = (sum x_(j)) / K                      var = (sum (x_(j) - mu)^2) / (K - 1)
+ *   A     = (sum |x_(j) - y|) / K                D   = sum (2j - K - 1) * x_(j)     (= sum of |x_a - x_b| over unordered pairs)
+ *   width = x_(K-m) - x_(1+m)                    r   = #{x_k < y} + floor(#{x_k == y} / 2), in [0, K]   (mid-rank: deterministic;
+ *                                                      ties only occur where the clip or a copy makes values equal)
+ * so that the ensemble CRPS is A - D / K^2 and the fair CRPS A - D / (K (K - 1)).  ACCUMULATED across samples and calls:
+ *   stats  (G, H, 9, I) doubles, ((g*H + h)*9 + n)*I + i:  [count, sum y, sum mu, sum (mu-y)^2, sum |mu-y|, sum var, sum A,
+ *          sum D, sum width]
+ *   hist   (G, H, K+1, I) uint32, ((g*H + h)*(K+1) + r)*I + i: how often the rank was r
+ * both node-contiguous.  One owning thread per cell adds the cell's samples in ascending s in registers and then adds to
+ * stats / hist once: no atomics, the same calls give the same bits; cells of a group that does not occur in `group` are
+ * neither read nor written; an id outside [0, G) skips the sample everywhere (the per-sample outputs included) and sets
+ * TECM_BAD_GROUP in *err_flag, never clamped.
+ * members are addressed as base[k*m_stride_k + s*m_stride_s + h*m_stride_h + i*m_stride_i], the target as in (3b), both
+ * read in place (element strides, 64-bit); lanes run along the nodes, so m_stride_i == 1 is the coalesced layout.
+ * Optional per-sample outputs (NULL skips one), float32 at out[s*o_stride_s + h*o_stride_h + i*o_stride_i]:
+ *   out_mean = mu, out_std = sqrt(var), out_lo = x_(1+m), out_hi = x_(K-m)  (physical units), and
+ *   out_mean_raw = the float64 mean over k ascending of the RAW members (non-finite -> 0): the ensemble-mean forecast in
+ *   scaled units, the form (3) and (3b) take.
+ * Limits: 2 <= K <= TECM_ENS_MAX_K, 0 <= 2*trim < K - 1, scale != 0, G and H <= 65535. */
+#define TECM_ENS_STATS 9
+#define TECM_ENS_MAX_K 64
+typedef struct {
+  const float* members; int64_t m_stride_k, m_stride_s, m_stride_h, m_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  int64_t S; int32_t H; int32_t G; int64_t I;          /* samples, horizons, groups, nodes */
+  int32_t K; int32_t trim;                             /* members, m */
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  int32_t _pad2;
+  double* stats;
+  uint32_t* hist;
+  const int32_t* group;
+  int32_t* err_flag;
+  float* out_mean; float* out_std; float* out_lo; float* out_hi; float* out_mean_raw;
+  int64_t o_stride_s, o_stride_h, o_stride_i;
+} TecmEnsemble;
+int tecm_ensemble_stats(const TecmEnsemble* e, void* stream);
+
 /* (4) sliding-window batch assembly from device-resident series (SlidingWindowSamplerDataset.__getitem__
  * src/data/dataset.py:65-99 + the harness reshapes train.py:62-65, :76): for sample b with window
  * start a = starts[b] (already multiplied by the dataset stride):

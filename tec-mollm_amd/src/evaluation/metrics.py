@@ -7,7 +7,8 @@ no sync, reads the model's permuted output view in place) and the 4 metrics x L_
 from 8*L_out doubles in `compute()` -- the only device->host copy of the whole evaluation.
 
 `MapMetrics` keeps the same statistics per (group, horizon, node) cell instead of per horizon (`tecm_metrics_map`), and
-`derive` turns statistics of any leading shape into the metrics, NaN where a cell saw no sample.
+`derive` turns statistics of any leading shape into the metrics, NaN where a cell saw no sample.  `EnsembleMetrics` scores a
+K-member ensemble per cell the same way (`tecm_ensemble_stats`: CRPS, spread, coverage, rank histogram; `derive_ensemble`).
 
 Same numbers as the reference: inverse StandardScaler transform, non-finite guards, clip of predictions
 to [0, 200] TECU, MAE / RMSE / R^2 (sklearn semantics) / Pearson r per horizon and their averages.
@@ -247,3 +248,138 @@ def evaluate_horizons(y_true_horizons_scaled, y_pred_horizons_scaled, target_sca
     hm = HorizonMetrics(t.shape[1], target_scaler_path, device=t.device)
     hm.update(p, t)
     return hm.compute()
+
+
+# ------------------------------------------------------------------------------------ ensembles
+ENSEMBLE_KEYS = ("count", "crps", "fair_crps", "rmse_mean", "mae_mean", "bias_mean", "spread", "spread_skill", "coverage",
+                 "interval_width")
+
+
+def nominal_coverage(members: int, trim: int) -> float:
+    """The share of the K + 1 equally likely ranks of the truth among K exchangeable members that lie inside the interval
+    [x_(1+m), x_(K-m)]: (K - 2m - 1) / (K + 1)."""
+    return (members - 2 * trim - 1) / (members + 1)
+
+
+def derive_ensemble(stats: np.ndarray, hist: np.ndarray, members: int, trim: int = 0) -> Dict[str, np.ndarray]:
+    """(..., 9) float64 sums [count, sum y, sum mu, sum (mu-y)^2, sum |mu-y|, sum var, sum A, sum D, sum width] and
+    (..., K+1) rank counts -> the ENSEMBLE_KEYS, arrays over the leading axes, NaN where a cell saw no sample:
+      crps = mean(A) - mean(D) / K^2                      fair_crps = mean(A) - mean(D) / (K (K - 1))
+      rmse_mean, mae_mean, bias_mean: of the ensemble mean against the truth (bias = mean(mu - y))
+      spread = sqrt(mean var)                             spread_skill = sqrt((K + 1) / K * mean var / MSE of the mean)
+      coverage = share of ranks in [m + 1, K - m - 1]     interval_width = mean(x_(K-m) - x_(1+m))
+    (1 for a spread_skill means the spread explains the error of the mean; it is inf or NaN where that error is 0)."""
+    K, m = int(members), int(trim)
+    st = np.asarray(stats, dtype=np.float64)
+    hs = np.asarray(hist, dtype=np.float64)
+    if st.shape[-1] != _lib.TECM_ENS_STATS or hs.shape[-1] != K + 1 or st.shape[:-1] != hs.shape[:-1]:
+        raise ValueError(f"stats (..., 9) and hist (..., {K + 1}) do not fit: {st.shape}, {hs.shape}")
+    if not (K >= 2 and 0 <= 2 * m < K - 1):
+        raise ValueError(f"needs members >= 2 and 0 <= 2 * trim < members - 1 (members {K}, trim {m})")
+    n, sy, smu, sse, sae, svar, sA, sD, sw = np.moveaxis(st, -1, 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mse, mvar = sse / n, svar / n
+        out = {"count": n.copy(),
+               "crps": (sA - sD / (K * K)) / n, "fair_crps": (sA - sD / (K * (K - 1))) / n,
+               "rmse_mean": np.sqrt(mse), "mae_mean": sae / n, "bias_mean": (smu - sy) / n,
+               "spread": np.sqrt(mvar), "spread_skill": np.sqrt((K + 1) / K * mvar / mse),
+               "coverage": hs[..., m + 1:K - m].sum(axis=-1) / n, "interval_width": sw / n}
+    empty = n == 0
+    for k in ENSEMBLE_KEYS[1:]:
+        out[k] = np.where(empty, np.nan, out[k])
+    return out
+
+
+def _pooled_ensemble(per: Dict[str, np.ndarray]) -> Dict[str, object]:
+    """`derive_ensemble` of (H, ...) rows -> per key its list by horizon and the average over the horizons."""
+    out: Dict[str, object] = {"count_by_horizon": per["count"].tolist()}
+    for k in ENSEMBLE_KEYS[1:]:
+        out[f"{k}_by_horizon"] = per[k].tolist()
+        out[f"{k}_avg"] = float(np.mean(per[k]))
+    return out
+
+
+class EnsembleMetrics:
+    """Probabilistic scores of a K-member ensemble per cell (group of the sample, horizon, node): CRPS and fair CRPS, the
+    error of the ensemble mean, spread, spread/skill, the coverage and width of the interval [x_(1+trim), x_(K-trim)] and
+    the rank histogram.  update(members, true, groups) per batch on the device (one kernel, `tecm_ensemble_stats`: the
+    members are not copied to the host, no atomics, so the same batches give the same bits), compute() at the end."""
+
+    def __init__(self, num_horizons: int, num_nodes: int, members: int, num_groups: int = 1, scaler=None, trim: int = 0,
+                 device: Union[str, torch.device] = "cuda"):
+        self.H, self.I, self.K, self.G, self.trim = int(num_horizons), int(num_nodes), int(members), int(num_groups), int(trim)
+        if min(self.H, self.I, self.G) < 1:
+            raise ValueError("EnsembleMetrics needs at least one horizon, one node and one group")
+        if not 2 <= self.K <= _lib.TECM_ENS_MAX_K:
+            raise ValueError(f"members must lie in [2, {_lib.TECM_ENS_MAX_K}], got {self.K}")
+        if not 0 <= 2 * self.trim < self.K - 1:
+            raise ValueError(f"trim must satisfy 0 <= 2 * trim < members - 1 (members {self.K}, trim {self.trim})")
+        self.scaler = _scaler_params(scaler)
+        # [g][h][k][i] and [g][h][r][i]: node-contiguous, the layout the kernel's lanes read and write
+        self.stats = torch.zeros(self.G, self.H, _lib.TECM_ENS_STATS, self.I, device=device, dtype=torch.float64)
+        self.hist = torch.zeros(self.G, self.H, self.K + 1, self.I, device=device, dtype=torch.int32)
+
+    @property
+    def nominal_coverage(self) -> float:
+        return nominal_coverage(self.K, self.trim)
+
+    def reset(self) -> None:
+        self.stats.zero_()
+        self.hist.zero_()
+
+    def update(self, members_scaled: torch.Tensor, y_true_scaled: torch.Tensor, groups: Optional[torch.Tensor] = None,
+               outputs=()) -> Dict[str, torch.Tensor]:
+        """members (K, S, H, N) or (K, S, H, N, 1) and the truth (S, H, N) or (S, H, N, 1), both in scaled units and read in
+        place whatever their strides (node-contiguous members are the coalesced layout); groups (S) int32 or None.
+        Returns the per-sample tensors named in `outputs` (`ops.ENSEMBLE_OUTPUTS`), each (S, H, N) float32: mean, std, lo,
+        hi in physical units, mean_raw in scaled units."""
+        from tecmollm import devcheck, ops
+        m = members_scaled
+        _lib.require_gpu_tensor(m, "members")
+        if m.dim() == 5 and m.shape[-1] == 1:
+            m = m.squeeze(-1)
+        if m.dim() != 4:
+            raise ValueError(f"members must be (K, S, H, N), got {tuple(members_scaled.shape)}")
+        t, S, H, I, ts, th, ti = _as_shi(y_true_scaled, "y_true")
+        if tuple(m.shape) != (self.K, S, H, I) or H != self.H or I != self.I:
+            raise ValueError(f"shape mismatch: members {tuple(members_scaled.shape)}, true {tuple(y_true_scaled.shape)}, "
+                             f"expected members {self.K}, horizons {self.H}, nodes {self.I}")
+        if groups is not None:
+            _lib.require_gpu_tensor(groups, "groups", torch.int32)
+            if groups.shape != (S,):
+                raise ValueError(f"groups must hold one id per sample: {tuple(groups.shape)} for {S} samples")
+            groups = groups.contiguous()
+        mean, scale = self.scaler if self.scaler is not None else (0.0, 1.0)
+        errs = devcheck.error_word(self.stats.device)
+        outs = {name: torch.empty(S, H, I, device=m.device, dtype=torch.float32) for name in outputs}
+        ops.ensemble_stats(m, t.as_strided((S, H, I), (ts, th, ti)), self.stats, self.hist, trim=self.trim, mean=mean,
+                           scale=scale, clip=(TEC_MIN, TEC_MAX) if self.scaler is not None else None, groups=groups,
+                           err_flag=errs.ptr(), outputs=outs)
+        if groups is not None:
+            errs.post()                        # only a group id can set the word here
+        return outs
+
+    def merge_(self, group=None) -> "EnsembleMetrics":
+        """Sum the statistics and the rank counts over the ranks of `group`, in place: both live in one buffer for the
+        length of ONE all-reduce (the counts as float64, exact below 2^53).  See `HorizonMetrics.merge_`."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            n = self.stats.numel()
+            flat = torch.cat([self.stats.reshape(-1), self.hist.reshape(-1).to(torch.float64)])
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+            self.stats.copy_(flat[:n].view_as(self.stats))
+            self.hist.copy_(flat[n:].view_as(self.hist).to(torch.int32))
+        return self
+
+    def compute(self) -> Dict[str, object]:
+        """The ENSEMBLE_KEYS as numpy (G, H, N) arrays, NaN where a cell saw no sample; "nominal_coverage" (a float);
+        "rank_histogram" (G, H, K+1), the rank counts pooled over the nodes; "by_group": per group the scores of its
+        statistics pooled over the nodes, by horizon and averaged over the horizons (NaN for a group never visited)."""
+        st = self.stats.permute(0, 1, 3, 2).cpu().numpy()                   # (G, H, I, 9)
+        hs = self.hist.permute(0, 1, 3, 2).cpu().numpy().astype(np.int64)   # (G, H, I, K+1)
+        out: Dict[str, object] = dict(derive_ensemble(st, hs, self.K, self.trim))
+        out["nominal_coverage"] = self.nominal_coverage
+        out["rank_histogram"] = hs.sum(axis=2)
+        out["by_group"] = [_pooled_ensemble(derive_ensemble(st[g].sum(axis=1), hs[g].sum(axis=1), self.K, self.trim))
+                           for g in range(self.G)]
+        return out

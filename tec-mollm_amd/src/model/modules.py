@@ -48,14 +48,20 @@ def precision_code(precision: str = "auto"):
     return bf16
 
 
+dropout_seed = F_.dropout_seed       # pins the base seed of every plan made inside it (tecmollm/functions.py)
+
+
 def make_plan(module: nn.Module, p: float = 0.1, precision: str = "auto") -> F_.DropPlan:
-    """One plan per forward call: dropout seeds (base seed = torch seed + call count) and the GEMM precision:
+    """One plan per forward call: dropout seeds (base seed = torch seed + call count, or the seed of the enclosing
+    `dropout_seed` context) and the GEMM precision:
     "fp32" = exact-f32 MFMA, "bf16" = bf16 MFMA with fp32 accumulate, "auto" = bf16 iff under bf16 autocast,
     "bf16x3" = fp32 emulated by three bf16 MFMAs per product on the plain GPT-2 GEMMs (opt-in, ~1e-5)."""
     _seed_counter[0] += 1
     bf16 = precision_code(precision)
-    return F_.DropPlan(training=module.training, p=p, base_seed=(torch.initial_seed() + 7919 * _seed_counter[0]),
-                       bf16=bf16)
+    base = F_.pinned_dropout_seed()
+    if base is None:
+        base = torch.initial_seed() + 7919 * _seed_counter[0]
+    return F_.DropPlan(training=module.training, p=p, base_seed=base, bf16=bf16)
 
 
 def _need_cuda(t: torch.Tensor, name: str):

@@ -3,13 +3,18 @@
 Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
   csrc/            hand-written HIP kernels + the C ABI (include/tecmollm.h at the repo root)
   tecmollm/        ctypes binding, autograd stage functions, graph preparation, training-step helpers, test-split evaluation,
-                   input attribution
+                   input attribution, ensemble forecasts and their scores
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/models/      mirror of the reference's baselines (`from src.models.baselines import HistoricalAverage`)
 """
 from ._lib import LIB_PATH, TecmError, lib  # noqa: F401
 from .devcheck import check_device_errors  # noqa: F401
 from .attribute import attribution_maps, input_gradient, integrated_gradients, write_attributions  # noqa: F401
+from .functions import dropout_seed  # noqa: F401
+from . import ensemble  # noqa: F401
+from .ensemble import (ensemble_forecast, ensemble_members, evaluate_ensemble, member_seed,  # noqa: F401
+                       write_ensemble)
 
 __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradient", "integrated_gradients",
-           "attribution_maps", "write_attributions"]
+           "attribution_maps", "write_attributions", "dropout_seed", "ensemble", "member_seed", "ensemble_members",
+           "ensemble_forecast", "evaluate_ensemble", "write_ensemble"]

@@ -124,6 +124,21 @@ class TecmMetricsMap(C.Structure):
     ]
 
 
+class TecmEnsemble(C.Structure):
+    _fields_ = [
+        ("members", c_f32p), ("m_stride_k", C.c_int64), ("m_stride_s", C.c_int64), ("m_stride_h", C.c_int64),
+        ("m_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("G", C.c_int32), ("I", C.c_int64),
+        ("K", C.c_int32), ("trim", C.c_int32),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("_pad2", C.c_int32),
+        ("stats", C.c_void_p), ("hist", C.c_void_p), ("group", C.c_void_p), ("err_flag", C.c_void_p),
+        ("out_mean", c_f32p), ("out_std", c_f32p), ("out_lo", c_f32p), ("out_hi", c_f32p), ("out_mean_raw", c_f32p),
+        ("o_stride_s", C.c_int64), ("o_stride_h", C.c_int64), ("o_stride_i", C.c_int64),
+    ]
+
+
 class TecmWindowBatch(C.Structure):
     _fields_ = [
         ("X", c_f32p), ("TF", c_f32p), ("Y", c_f32p), ("starts", C.c_void_p), ("starts_host_check", C.c_void_p),
@@ -175,6 +190,8 @@ class TecmConvFwd(C.Structure):
 TECM_NORM_BLOCKS = 512
 TECM_METRIC_STATS = 8
 TECM_MAP_LDS_MAX_H = 32
+TECM_ENS_STATS = 9
+TECM_ENS_MAX_K = 64
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
 
 
@@ -259,6 +276,7 @@ EXPORTS = {
     "tecm_seed_advance": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "tecm_metrics_accumulate": (C.c_int, [C.POINTER(TecmMetrics), C.c_void_p]),
     "tecm_metrics_map": (C.c_int, [C.POINTER(TecmMetricsMap), C.c_void_p]),
+    "tecm_ensemble_stats": (C.c_int, [C.POINTER(TecmEnsemble), C.c_void_p]),
     "tecm_window_batch": (C.c_int, [C.POINTER(TecmWindowBatch), C.c_void_p]),
     "tecm_window_baseline": (C.c_int, [C.POINTER(TecmWindowBaseline), C.c_void_p]),
     "tecm_slot_mean": (C.c_int, [C.POINTER(TecmSlotMean), C.c_void_p]),

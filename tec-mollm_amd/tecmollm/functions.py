@@ -9,6 +9,7 @@ All activations after the spatial stage are time-major (B, T, N, C): row m = (b*
 """
 from __future__ import annotations
 
+import contextlib
 import os
 from dataclasses import dataclass
 import weakref
@@ -84,6 +85,29 @@ class DropPlan:
         if not self.training or self.p <= 0.0:
             return None
         return drop(self.p, ops.splitmix64(self.base_seed * 1000003 + site), ld)
+
+
+_seed_override: List[Optional[int]] = [None]           # the base seed of every plan made inside `dropout_seed`, None outside
+
+
+@contextlib.contextmanager
+def dropout_seed(base_seed: int):
+    """Every forward called inside this context draws its dropout masks from `base_seed` (`DropPlan.base_seed`) instead of
+    torch's seed and the call counter (`src/model/modules.py:make_plan`): two training-mode forwards under the same seed
+    drop the same elements.  Contexts nest; leaving one restores the seed of the enclosing one, or the counter-derived
+    seeds outside all of them.  The call counter advances inside as it does outside, so the masks of the forwards after
+    the context do not depend on whether a seed was pinned before them."""
+    prev = _seed_override[0]
+    _seed_override[0] = int(base_seed)
+    try:
+        yield
+    finally:
+        _seed_override[0] = prev
+
+
+def pinned_dropout_seed() -> Optional[int]:
+    """The base seed of the innermost active `dropout_seed` context, None outside."""
+    return _seed_override[0]
 
 
 def _lib_error(msg: str):

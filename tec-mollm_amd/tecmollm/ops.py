@@ -699,3 +699,49 @@ def transpose_scale(src: torch.Tensor, lds: int, dst: torch.Tensor, ldd: int, ro
     """dst[r*ldd + c] = scale * src[c*lds + r]."""
     check(lib().tecm_transpose_scale(src.data_ptr(), lds, _off(dst, dst_off), ldd, rows, cols, scale, stream_ptr()),
           "tecm_transpose_scale")
+
+
+ENSEMBLE_OUTPUTS = ("mean", "std", "lo", "hi", "mean_raw")
+
+
+def ensemble_stats(members: torch.Tensor, target: torch.Tensor, stats: torch.Tensor, hist: torch.Tensor, *, trim: int = 0,
+                   mean: float = 0.0, scale: float = 1.0, clip: Optional[Tuple[float, float]] = None,
+                   groups: Optional[torch.Tensor] = None, err_flag: int = 0,
+                   outputs: Optional[dict] = None) -> None:
+    """tecm_ensemble_stats (include/tecmollm.h (3c)): one update of `stats` (G, H, 9, I) float64 and `hist` (G, H, K+1, I)
+    int32 (read as unsigned counts) from `members` (K, S, H, I) and `target` (S, H, I), float32 views of any strides, read in
+    place.  `clip` = (lo, hi) clamps the members after the inverse transform (mean, scale); `groups` (S) int32 or None;
+    `err_flag` is the address of the device error word (tecmollm/devcheck.py).  `outputs` maps names of ENSEMBLE_OUTPUTS to
+    (S, H, I) float32 tensors that all have the strides of the first one; names left out are not written."""
+    K, S, H, I = members.shape
+    G = stats.shape[0]
+    if target.shape != (S, H, I):
+        raise ValueError(f"target must be (S, H, I) = {(S, H, I)}, got {tuple(target.shape)}")
+    if stats.shape != (G, H, _lib.TECM_ENS_STATS, I) or stats.dtype != torch.float64 or not stats.is_contiguous():
+        raise ValueError(f"stats must be a contiguous float64 (G, {H}, {_lib.TECM_ENS_STATS}, {I}) tensor")
+    if hist.shape != (G, H, K + 1, I) or hist.dtype != torch.int32 or not hist.is_contiguous():
+        raise ValueError(f"hist must be a contiguous int32 ({G}, {H}, {K + 1}, {I}) tensor")
+    outs = dict(outputs or {})
+    unknown = set(outs) - set(ENSEMBLE_OUTPUTS)
+    if unknown:
+        raise ValueError(f"outputs must come from {ENSEMBLE_OUTPUTS}, got {sorted(unknown)}")
+    o_strides = (0, 0, 0)
+    for name, t in outs.items():
+        _lib.require_gpu_tensor(t, name)
+        if t.shape != (S, H, I):
+            raise ValueError(f"output {name} must be (S, H, I) = {(S, H, I)}, got {tuple(t.shape)}")
+        if o_strides == (0, 0, 0):
+            o_strides = tuple(t.stride())
+        elif tuple(t.stride()) != o_strides:
+            raise ValueError("the per-sample outputs must share their strides")
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    e = _lib.TecmEnsemble(members=members.data_ptr(), m_stride_k=members.stride(0), m_stride_s=members.stride(1),
+                          m_stride_h=members.stride(2), m_stride_i=members.stride(3),
+                          target=target.data_ptr(), t_stride_s=target.stride(0), t_stride_h=target.stride(1),
+                          t_stride_i=target.stride(2), S=S, H=H, G=G, I=I, K=K, trim=int(trim),
+                          mean=float(mean), scale=float(scale), clip_lo=lo, clip_hi=hi, clip=1 if clip is not None else 0,
+                          stats=stats.data_ptr(), hist=hist.data_ptr(), group=ptr(groups), err_flag=err_flag or None,
+                          out_mean=ptr(outs.get("mean")), out_std=ptr(outs.get("std")), out_lo=ptr(outs.get("lo")),
+                          out_hi=ptr(outs.get("hi")), out_mean_raw=ptr(outs.get("mean_raw")),
+                          o_stride_s=o_strides[0], o_stride_h=o_strides[1], o_stride_i=o_strides[2])
+    check(lib().tecm_ensemble_stats(C.byref(e), stream_ptr()), "tecm_ensemble_stats")

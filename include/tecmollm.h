@@ -252,6 +252,49 @@ typedef struct TecmSpatialDx {
 int64_t tecm_spatial_dx_ws_floats(const TecmSpatial* d);
 int tecm_spatial_dx(const TecmSpatial* d, const TecmSpatialDx* g, void* stream);
 
+/* The GATv2 attention coefficients of the same stage (csrc/spatial_attn.hip): what PyG's GATv2Conv returns for
+ * return_attention_weights=True at the reference's call site (modules.py:329-336,:356), before the attention dropout:
+ *   alpha_ij = exp(e_ij - max_j e_ij) / (sum_j exp(e_ij - max) + 1e-16),  e_ij = att_k . lrelu(x_l[j,k] + x_r[i,k])
+ * over the in-edges j of target i plus its self loop, per head, per graph.  It takes the descriptor the forward ran with: the
+ * fused stage (flags == 0, Cin 6 or 10, Demb = 22 - Cin) or the stand-alone GATv2 (TECM_SPATIAL_NO_RESIDUAL, Cin = 22,
+ * Demb = 0); the tiling fields of `d` are checked but not used, alpha_drop is ignored, `out` is not written.
+ * Entries of a graph in KERNEL ORDER: the by-target CSR entries q in [0, E) in rowptr / colidx order, then the N self loops
+ * at E + i; E2 = E + N.  A graph g = t*B + b >= graphs_with_edges holds its self loops only: alpha = 1 there, 0 in every
+ * CSR entry, entropy 0, all exact.  A time index outside its table gives NaN coefficients in the graph's rows that read it
+ * and sets TECM_BAD_* in *d->err_flag.
+ *   raw export    alpha (B*L, E2, H) floats, graphs in memory order gm = b*L + t: entry q of graph gm, head h, is written at
+ *                 alpha[(gm*E2 + p(q))*H + h] with p(q) = perm[q] for a CSR entry (perm NULL: q) and p(E + i) = E + i.  With
+ *                 perm = the position of every CSR entry in the caller's edge list the export is in PyG's order: the
+ *                 non-self edges as given, then the self loops.  A perm value outside [0, E2) drops that entry.
+ *   accumulation  edge_stats (G, 3, E2, H) doubles in kernel order: sum alpha, sum alpha^2, sum m with the message size
+ *                 m_ij = alpha_ij * |x_l[j, head]|_2;  node_stats (G, N, H) doubles: sum of the entropy -sum_j alpha ln alpha
+ *                 of target i;  counts (G) int64: graphs added.  group (B*L) int32 in memory order names the group of every
+ *                 graph (NULL: group 0); an id outside [0, num_groups) skips the graph and sets TECM_BAD_GROUP in
+ *                 *d->err_flag, never clamped.  TECM_ATTN_SKIP_UNCONNECTED leaves the graphs without edges out of every sum.
+ *                 Every cell has ONE owning thread, which adds the graphs of the call in ascending gm with plain loads and
+ *                 stores: no atomics, so the same calls in the same order give the same bits, whatever the workspace size.
+ * Either part may be left out (alpha NULL / edge_stats NULL), not both.
+ * ws: the call walks chunks of graphs through it (x_l, x_r as 24-float rows; alpha, m and the entropy of the chunk when
+ * accumulating).  ws_floats = floats it holds, 0 = tecm_spatial_attention_ws_floats(d, a), which is at most 64 MiB unless one
+ * graph needs more; any size that holds one graph is accepted (smaller: more chunks, same bits). */
+#define TECM_ATTN_SKIP_UNCONNECTED 1
+typedef struct TecmSpatialAttn {
+  float* alpha;                           /* (B*L, E2, H) or NULL */
+  const int32_t* perm;                    /* (E) or NULL = identity */
+  double* edge_stats;                     /* (G, 3, E2, H) or NULL = no accumulation */
+  double* node_stats;                     /* (G, N, H) */
+  int64_t* counts;                        /* (G) */
+  const int32_t* group;                   /* (B*L) or NULL */
+  float* ws; int64_t ws_floats;           /* 16-byte aligned; contents undefined after */
+  int32_t num_groups;                     /* G */
+  int32_t E;                              /* entries of the by-target CSR: rowptr[N] */
+  int32_t flags;                          /* TECM_ATTN_* */
+  int32_t _pad;
+} TecmSpatialAttn;
+/* Floats of workspace the call asks for by default, or 0 when (d, a) is not served.  Pure host function. */
+int64_t tecm_spatial_attention_ws_floats(const TecmSpatial* d, const TecmSpatialAttn* a);
+int tecm_spatial_attention(const TecmSpatial* d, const TecmSpatialAttn* a, void* stream);
+
 /* ------------------------------------------------------------------ stage a-4 normalisation
  * nn.GroupNorm(1, C) + nn.GELU() (modules.py:28-29) for the three parallel branches at once.
  * y/act: (B, L, N, CT) time-major with CT = 3*Cout (branch j owns channels [j*Cout,(j+1)*Cout)).

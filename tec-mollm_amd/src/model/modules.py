@@ -440,10 +440,14 @@ class SpatialEncoder(nn.Module):
         g = self.gat_conv
         return (g.lin_l.weight, g.lin_l.bias, g.lin_r.weight, g.lin_r.bias, g.att, g.bias)
 
-    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, edge_index: torch.Tensor, edge_weight: Optional[torch.Tensor] = None,
+                return_attention_weights: Optional[bool] = None):
         """Reference signature (modules.py:340-359): x (num_graphs, N, C_in) -> (num_graphs, N, heads * out_channels);
         edge_weight is ignored as in the reference.  Stand-alone use only (TEC_MoLLM.forward fuses this with the
-        embedding and the residual); gradients reach the GATv2 parameters, x must not require grad."""
+        embedding and the residual); gradients reach the GATv2 parameters, x must not require grad.
+        `return_attention_weights` truthy (PyG's keyword at modules.py:356): returns (out, (edge_index_sl, alpha)) with
+        edge_index_sl (2, E'') the non-self edges as given followed by one self loop per node and alpha (num_graphs, E'',
+        heads) the coefficients before dropout (tecmollm/spatial_attention.py); `out` is unchanged by the keyword."""
         _need_cuda(x, "x")
         if x.dim() != 3 or x.shape[2] != self.output_channels:
             raise ValueError(f"x must be (num_graphs, N, {self.output_channels})")
@@ -451,7 +455,11 @@ class SpatialEncoder(nn.Module):
         meta = graph_.get(edge_index, N, x.device, 0)
         plan = make_plan(self, self.dropout, precision="fp32")
         R = 1 if self.gat_graphs == "reference" else G
-        return F_.GatFn.apply(x, *self.params(), meta, self.heads, R, plan)
+        out = F_.GatFn.apply(x, *self.params(), meta, self.heads, R, plan)
+        if return_attention_weights:
+            from tecmollm.spatial_attention import encoder_attention
+            return out, encoder_attention(self, x, edge_index)
+        return out
 
 
 class PredictionHead(nn.Module):

@@ -3,7 +3,7 @@
 Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
   csrc/            hand-written HIP kernels + the C ABI (include/tecmollm.h at the repo root)
   tecmollm/        ctypes binding, autograd stage functions, graph preparation, training-step helpers, test-split evaluation,
-                   input attribution, ensemble forecasts and their scores
+                   input attribution, ensemble forecasts and their scores, spatial attention maps
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/models/      mirror of the reference's baselines (`from src.models.baselines import HistoricalAverage`)
 """
@@ -14,7 +14,11 @@ from .functions import dropout_seed  # noqa: F401
 from . import ensemble  # noqa: F401
 from .ensemble import (ensemble_forecast, ensemble_members, evaluate_ensemble, member_seed,  # noqa: F401
                        write_ensemble)
+from .spatial_attention import (AttentionStats, attention_maps, evaluate_attention, graph_groups_by_lag,  # noqa: F401
+                                graph_groups_by_sample, graph_groups_by_slot, spatial_attention, write_attention)
 
 __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradient", "integrated_gradients",
            "attribution_maps", "write_attributions", "dropout_seed", "ensemble", "member_seed", "ensemble_members",
-           "ensemble_forecast", "evaluate_ensemble", "write_ensemble"]
+           "ensemble_forecast", "evaluate_ensemble", "write_ensemble", "spatial_attention", "AttentionStats",
+           "evaluate_attention", "attention_maps", "write_attention", "graph_groups_by_sample", "graph_groups_by_slot",
+           "graph_groups_by_lag"]

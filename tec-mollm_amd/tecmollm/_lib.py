@@ -83,6 +83,14 @@ class TecmSpatialDx(C.Structure):
     ]
 
 
+class TecmSpatialAttn(C.Structure):
+    _fields_ = [
+        ("alpha", c_f32p), ("perm", C.c_void_p), ("edge_stats", C.c_void_p), ("node_stats", C.c_void_p),
+        ("counts", C.c_void_p), ("group", C.c_void_p), ("ws", c_f32p), ("ws_floats", C.c_int64),
+        ("num_groups", C.c_int32), ("E", C.c_int32), ("flags", C.c_int32), ("_pad", C.c_int32),
+    ]
+
+
 class TecmLnAdd(C.Structure):
     _fields_ = [("dy2", C.c_void_p), ("ld", C.c_int64), ("bf16", C.c_int32), ("_pad", C.c_int32), ("drop", TecmDrop)]
 
@@ -192,6 +200,7 @@ TECM_METRIC_STATS = 8
 TECM_MAP_LDS_MAX_H = 32
 TECM_ENS_STATS = 9
 TECM_ENS_MAX_K = 64
+TECM_ATTN_SKIP_UNCONNECTED = 1
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
 
 
@@ -214,6 +223,8 @@ EXPORTS = {
     "tecm_spatial_bwd2": (C.c_int, [C.POINTER(TecmSpatial), C.POINTER(TecmSpatialGrads), c_f32p, C.c_void_p]),
     "tecm_spatial_dx_ws_floats": (C.c_int64, [C.POINTER(TecmSpatial)]),
     "tecm_spatial_dx": (C.c_int, [C.POINTER(TecmSpatial), C.POINTER(TecmSpatialDx), C.c_void_p]),
+    "tecm_spatial_attention_ws_floats": (C.c_int64, [C.POINTER(TecmSpatial), C.POINTER(TecmSpatialAttn)]),
+    "tecm_spatial_attention": (C.c_int, [C.POINTER(TecmSpatial), C.POINTER(TecmSpatialAttn), C.c_void_p]),
     "tecm_groupnorm_gelu_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
     "tecm_gn_y16_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),

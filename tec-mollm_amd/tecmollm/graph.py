@@ -40,6 +40,9 @@ class GraphMeta:
     out_ptr: torch.Tensor      # int32 (N+1)
     out_target: torch.Tensor   # int32 (E'): target of the entry
     out_slot: torch.Tensor     # int32 (E'): its position in the target's list: colidx[rowptr[target] + slot] == j
+    # the attention export (csrc/spatial_attn.hip): for every by-target CSR entry q, the position of that edge in the given
+    # edge_index once its self loops are stripped -- PyG's edge order
+    edge_pos: torch.Tensor     # int32 (E')
 
 
 def csr_by_target(edge_index: np.ndarray, num_nodes: int) -> Tuple[np.ndarray, np.ndarray]:
@@ -54,6 +57,13 @@ def csr_by_target(edge_index: np.ndarray, num_nodes: int) -> Tuple[np.ndarray, n
     np.add.at(rowptr, dst + 1, 1)
     rowptr = np.cumsum(rowptr)
     return rowptr.astype(np.int32), src.astype(np.int32)
+
+
+def csr_edge_pos(edge_index: np.ndarray) -> np.ndarray:
+    """For every entry q of `csr_by_target`'s CSR, the position of that edge in `edge_index` with its self loops stripped:
+    the stable sort by target that `csr_by_target` applies, as a map from CSR entries to the given (PyG) edge order."""
+    src, dst = edge_index[0].astype(np.int64), edge_index[1].astype(np.int64)
+    return np.argsort(dst[src != dst], kind="stable").astype(np.int32)
 
 
 def tile_windows(rowptr: np.ndarray, colidx: np.ndarray, num_nodes: int, tile_nodes: int):
@@ -159,7 +169,8 @@ def build(edge_index: torch.Tensor, num_nodes: int, device: torch.device, demb: 
                      rowptr=to(rowptr),
                      colidx=to(colidx if colidx.size else np.zeros(1, np.int32)), tile_lo=to(lo), tile_hi=to(hi),
                      src_ptr=to(sp), src_col=to(sc), src_ptr_off=to(so),
-                     out_ptr=to(op), out_target=to(some(ot)), out_slot=to(some(os_)))
+                     out_ptr=to(op), out_target=to(some(ot)), out_slot=to(some(os_)),
+                     edge_pos=to(some(csr_edge_pos(ei))))
 
 
 _cache: Dict[Tuple[int, int, int, str], Tuple[torch.Tensor, GraphMeta]] = {}

@@ -745,3 +745,57 @@ def ensemble_stats(members: torch.Tensor, target: torch.Tensor, stats: torch.Ten
                           out_hi=ptr(outs.get("hi")), out_mean_raw=ptr(outs.get("mean_raw")),
                           o_stride_s=o_strides[0], o_stride_h=o_strides[1], o_stride_i=o_strides[2])
     check(lib().tecm_ensemble_stats(C.byref(e), stream_ptr()), "tecm_ensemble_stats")
+
+
+def spatial_attention_ws_floats(d: "_lib.TecmSpatial", num_edges: int, accumulate: bool) -> int:
+    """tecm_spatial_attention_ws_floats: floats of workspace the call asks for by default (one chunk of graphs, at most
+    64 MiB unless one graph needs more), 0 when the descriptor is not served.  Pure host arithmetic."""
+    a = _lib.TecmSpatialAttn(E=int(num_edges), edge_stats=8 if accumulate else None)   # only NULL / non-NULL is read
+    return int(lib().tecm_spatial_attention_ws_floats(C.byref(d), C.byref(a)))
+
+
+def spatial_attention(d: "_lib.TecmSpatial", num_edges: int, *, alpha: Optional[torch.Tensor] = None,
+                      perm: Optional[torch.Tensor] = None, edge_stats: Optional[torch.Tensor] = None,
+                      node_stats: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                      groups: Optional[torch.Tensor] = None, skip_unconnected: bool = False,
+                      max_ws_bytes: Optional[int] = None) -> None:
+    """tecm_spatial_attention (include/tecmollm.h, csrc/spatial_attn.hip) for the spatial descriptor `d` a forward would run
+    with and the `num_edges` = E' entries of its by-target CSR.  `alpha` (B*L, E'' = E' + N, H) float32 receives the
+    coefficients, entry q of the CSR at position perm[q] (int32 (E'), None: q), the self loops behind them; `edge_stats`
+    (G, 3, E'', H), `node_stats` (G, N, H) float64 and `counts` (G) int64 are added to, in kernel order, with `groups` (B*L)
+    int32 naming every graph's group.  `max_ws_bytes` caps the workspace (it must hold one graph): the call then walks
+    more chunks of graphs and returns the same bits."""
+    G_, N, H = d.B * d.L, d.N, d.H
+    E2 = int(num_edges) + N
+    dev = torch.device("cuda", torch.cuda.current_device())
+    for name, t, shape, dtype in (("alpha", alpha, (G_, E2, H), torch.float32), ("perm", perm, (int(num_edges),), torch.int32),
+                                  ("groups", groups, (G_,), torch.int32)):
+        if t is not None:
+            _lib.require_gpu_tensor(t, name, dtype)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+            dev = t.device
+    ng = 0
+    if edge_stats is not None:
+        ng = edge_stats.shape[0]
+        for name, t, shape, dtype in (("edge_stats", edge_stats, (ng, 3, E2, H), torch.float64),
+                                      ("node_stats", node_stats, (ng, N, H), torch.float64),
+                                      ("counts", counts, (ng,), torch.int64)):
+            if t is None:
+                raise ValueError("the statistics need edge_stats, node_stats and counts together")
+            _lib.require_gpu_tensor(t, name, dtype)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+        dev = edge_stats.device
+    nws = spatial_attention_ws_floats(d, num_edges, edge_stats is not None)
+    if nws <= 0:
+        raise _lib.TecmError("spatial_attention: serves 22 channels in 2 heads: the fused stage with C_in 6 or 10 and "
+                             f"d_emb = 22 - C_in, or the stand-alone GATv2 on 22 channels (got C_in = {d.Cin}, d_emb = {d.Demb}, "
+                             f"heads = {d.H})")
+    if max_ws_bytes is not None:
+        nws = min(nws, int(max_ws_bytes) // 4)
+    ws = torch.empty(nws, device=dev, dtype=torch.float32)
+    a = _lib.TecmSpatialAttn(alpha=ptr(alpha), perm=ptr(perm), edge_stats=ptr(edge_stats), node_stats=ptr(node_stats),
+                             counts=ptr(counts), group=ptr(groups), ws=ws.data_ptr(), ws_floats=nws, num_groups=ng,
+                             E=int(num_edges), flags=_lib.TECM_ATTN_SKIP_UNCONNECTED if skip_unconnected else 0)
+    check(lib().tecm_spatial_attention(C.byref(d), C.byref(a), stream_ptr()), "tecm_spatial_attention")

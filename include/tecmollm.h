@@ -752,6 +752,64 @@ typedef struct {
 } TecmSlotMean;
 int tecm_slot_mean(const TecmSlotMean* m, void* stream);
 
+/* (7) SarimaBaseline (src/models/baselines.py:47-72) on the device: a seasonal ARMA on the differenced series in subset
+ * (additive) form, estimated per node by the two-stage Hannan-Rissanen regression.  NOT statsmodels' exact-likelihood
+ * multiplicative SARIMAX: the lags of the expanded product polynomials each carry a free coefficient, there is no constant,
+ * and nothing iterates.  Everything below is fp64; the series is fp32.
+ *   lags      ar_lags[n_ar], ma_lags[n_ma] ascending and positive, K = n_ar + n_ma in [1, TECM_SAR_MAX_K], the largest lag
+ *             Lmax <= TECM_SAR_MAX_LAG, Lmax <= m <= TECM_SAR_MAX_LONG_AR, d and D in {0, 1}, s >= 1 when D = 1, and the
+ *             differencing offset o = d + s*D <= TECM_SAR_MAX_OFFSET.
+ *   w_u       = (y_t - y_{t-1}) - (y_{t-s} - y_{t-s-1}) with t = u + o (d = D = 1; y_t - y_{t-1} for d alone, y_t - y_{t-s}
+ *             for D alone, y_t for neither), u < n = T - o.
+ *   stage 1   autocov[k] = (1/n) sum_{u=k}^{n-1} w_u w_{u-k}, k <= m; Levinson-Durbin gives the long AR phi^(m);
+ *             e_u = w_u - sum_{i<=m} phi_i w_{u-i}, u >= m.
+ *   stage 2   rows u = m + Lmax .. n-1, z_u = [w_{u-a}]_{a in ar_lags} ++ [e_{u-b}]_{b in ma_lags}; gram = [G | r] with
+ *             G = sum z z^T, r = sum z w_u; Cholesky solve -> coef = (phi_A, theta_M); sigma2 = residual mean square
+ *             (wss - 2 coef.r + coef.G.coef) / rows with wss = sum w_u^2 over the rows.
+ *   status    TECM_SAR_NONFINITE: a NaN / inf in the node's series (coef and sigma2 NaN).  TECM_SAR_DEGENERATE: autocov[0] <= 0,
+ *             a Levinson variance <= 0, a Cholesky pivot <= 1e-12 G_kk, or n < m + Lmax + 2K (coef 0, sigma2 = autocov[0]: the
+ *             forecast is then the differencing rule alone).  TECM_SAR_MA_DROPPED: solved with use_ma[node] == 0.
+ * tecm_sar_fit: x addressed by element strides ((T, N) data, or one channel of (T, N*C) in place).  The time axis is cut
+ * into fixed chunks of TECM_SAR_CHUNK steps of u; a block (64 nodes, lanes along nodes) sums one chunk in ascending time
+ * after rebuilding its rings of w and e from the steps before it, and the chunks are joined in ascending order: no atomics,
+ * two calls return identical bits.  ws: tecm_sar_fit_ws_bytes() bytes, 8-byte aligned.
+ * tecm_sar_solve: solves again from gram / wss / autocov (as tecm_sar_fit left them); use_ma (N) int8 or NULL; a node with
+ * use_ma == 0 solves the leading n_ar x n_ar block with theta = 0.  Keeps the stage-1 bits of status. */
+enum { TECM_SAR_MAX_K = 12, TECM_SAR_MAX_LAG = 32, TECM_SAR_MAX_LONG_AR = 64, TECM_SAR_MAX_OFFSET = 64, TECM_SAR_CHUNK = 1024 };
+enum { TECM_SAR_DEGENERATE = 1, TECM_SAR_NONFINITE = 2, TECM_SAR_MA_DROPPED = 4 };
+typedef struct {
+  const float* x; int64_t stride_t, stride_n;
+  int64_t T;
+  int32_t N, d, D, s, m, n_ar, n_ma, _pad;
+  int32_t ar_lags[12], ma_lags[12];
+  double* autocov;        /* (N, m+1) */
+  double* gram;           /* (N, K, K+1) = [G | r] */
+  double* wss;            /* (N) sum of w_u^2 over the stage-2 rows */
+  double* coef;           /* (N, K) */
+  double* sigma2;         /* (N) */
+  int32_t* status;        /* (N) */
+  const int8_t* use_ma;   /* (N) or NULL; read by tecm_sar_solve only */
+  double* ws;             /* tecm_sar_fit only */
+} TecmSarFit;
+int64_t tecm_sar_fit_ws_bytes(const TecmSarFit* f);     /* pure host arithmetic; -1 on a bad descriptor */
+int tecm_sar_fit(const TecmSarFit* f, void* stream);
+int tecm_sar_solve(const TecmSarFit* f, void* stream);
+
+/* SarimaBaseline's forecast (src/models/baselines.py:64-72, there only from the end of the training series) for every window
+ * of a split in one launch: TecmWindowBaseline's fields (mode and period unused; o_stride_h != 0 when L_out > 1) plus the
+ * coefficients.  For window b, node n, in fp64: w over the window; e_u = 0 for u < Lmax, then e_u = w_u - sum phi_a w_{u-a}
+ * - sum theta_b e_{u-b}; for the future w^_u = sum phi_a w_{u-a} + sum theta_b e_{u-b} with future e = 0 and future w = w^;
+ * y^ = w^ integrated back through the differencing rule, earlier forecasts standing in where a lag reaches them; rounded to
+ * fp32 at the store.  Needs L_in >= o + Lmax + 1.  coef (N, K) doubles as tecm_sar_fit writes it.  A window outside
+ * [0, T - L_in] that reaches the kernel is written as NaN, never read. */
+typedef struct {
+  TecmWindowBaseline w;
+  const double* coef;
+  int32_t d, D, s, n_ar, n_ma, _pad;
+  int32_t ar_lags[12], ma_lags[12];
+} TecmSarForecast;
+int tecm_sar_forecast(const TecmSarForecast* f, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

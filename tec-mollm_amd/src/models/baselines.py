@@ -6,19 +6,29 @@ kernel (`tecm_slot_mean`) returns the (N, 12) table from a series that already l
 order, so the table does not depend on the launch.  The series is read as float32, the dtype the processed splits
 carry; a float64 input is rounded to it first.  `predict` (:35-45) is a row gather.
 
-`SarimaBaseline` (:47-72) is NOT provided: it is a thin wrapper around statsmodels' SARIMAX, a host library this
-project neither ships nor replaces.
+`SarimaBaseline` (:47-72) keeps the reference's constructor and its two methods, but NOT its estimator.  The reference
+wraps statsmodels' SARIMAX: an exact Gaussian likelihood of the multiplicative model, maximised iteratively on the host,
+one node at a time.  Here the model is the SUBSET (additive) seasonal ARMA on the differenced series -- every lag of the
+expanded product polynomials carries a free coefficient, so the default (1,1,1)(1,1,1,12) has AR and MA lags {1, 12, 13}
+with three free coefficients each where the multiplicative model ties the third to the product of the other two -- and
+it is estimated by the two-stage Hannan-Rissanen regression: a long autoregression (Levinson-Durbin on the sample
+autocovariances) supplies innovation estimates, and one least-squares solve on lagged values and lagged innovations gives
+the coefficients.  All linear algebra in fp64, no iteration, no constant term; every node of a split is fitted by one
+call (`tecm_sar_fit`), and every window of a test split is forecast by one launch (`tecm_sar_forecast`), which the
+reference's class cannot do at all (it forecasts from the end of the training series only).  The estimates are
+consistent but not the maximum-likelihood ones: expect coefficients and forecasts close to, not equal to, statsmodels'.
 """
 from __future__ import annotations
 
 import ctypes as C
 import logging
-from typing import Union
+from typing import Sequence, Union
 
 import numpy as np
 import torch
 
-from tecmollm._lib import TecmSlotMean, check, lib, require_gpu_tensor, stream_ptr
+from tecmollm import _lib
+from tecmollm._lib import TecmSarFit, TecmSarForecast, TecmSlotMean, TecmWindowBaseline, check, lib, require_gpu_tensor, stream_ptr
 
 log = logging.getLogger(__name__)
 
@@ -90,6 +100,235 @@ class HistoricalAverage:
         slots = torch.as_tensor(time_slots(time_data)).to(self._table.device)
         pred = self._table.index_select(0, slots)
         return pred if isinstance(time_data, torch.Tensor) and time_data.is_cuda else pred.cpu().numpy()
+
+
+def sarima_lags(order, seasonal_order, long_ar=None):
+    """(p, d, q), (P, D, Q, s) -> (d, D, s, ar_lags, ma_lags, m): the lags of the expanded product polynomials,
+    { i + s j : 0 <= i <= p, 0 <= j <= P } without 0 (likewise q, Q), and the order m of the long autoregression
+    (default 2 Lmax clipped to [8, 64]).  Raises ValueError outside the ranges the kernels serve."""
+    try:
+        p, d, q = (int(v) for v in order)
+        P, D, Q, s = (int(v) for v in seasonal_order)
+    except (TypeError, ValueError):
+        raise ValueError(f"order must be (p, d, q) and seasonal_order (P, D, Q, s), got {order!r} and {seasonal_order!r}")
+    if min(p, q, P, Q) < 0:
+        raise ValueError("p, q, P, Q must not be negative")
+    if d not in (0, 1) or D not in (0, 1):
+        raise ValueError(f"d and D must be 0 or 1, got d = {d}, D = {D}")
+    if (P or Q or D) and s < 1:
+        raise ValueError(f"a seasonal term needs a period s >= 1, got {s}")
+    if not (P or Q or D):
+        s = max(s, 0)
+    ar = sorted({i + s * j for i in range(p + 1) for j in range(P + 1)} - {0})
+    ma = sorted({i + s * j for i in range(q + 1) for j in range(Q + 1)} - {0})
+    K = len(ar) + len(ma)
+    if not 1 <= K <= _lib.TECM_SAR_MAX_K:
+        raise ValueError(f"the model must have between 1 and {_lib.TECM_SAR_MAX_K} coefficients, this one has {K}")
+    lmax = max(ar + ma)
+    if lmax > _lib.TECM_SAR_MAX_LAG:
+        raise ValueError(f"the largest lag is {lmax}; at most {_lib.TECM_SAR_MAX_LAG} is served")
+    if d + s * D > _lib.TECM_SAR_MAX_OFFSET:
+        raise ValueError(f"the differencing offset d + s D is {d + s * D}; at most {_lib.TECM_SAR_MAX_OFFSET} is served")
+    m = min(max(2 * lmax, 8), _lib.TECM_SAR_MAX_LONG_AR) if long_ar is None else int(long_ar)
+    if not lmax <= m <= _lib.TECM_SAR_MAX_LONG_AR:
+        raise ValueError(f"long_ar must lie in [{lmax}, {_lib.TECM_SAR_MAX_LONG_AR}], got {m}")
+    return d, D, s, ar, ma, m
+
+
+def ma_invertible(theta: np.ndarray, ma_lags) -> np.ndarray:
+    """(N, len(ma_lags)) coefficients -> (N,) bool: every root of 1 + sum_b theta_b z^b lies outside the unit circle, i.e.
+    every eigenvalue of the companion matrix of x^L + theta_1 x^(L-1) + ... + theta_L (x = 1 / z) is inside it.  A row
+    with a NaN counts as invertible (there is nothing to repair)."""
+    theta = np.atleast_2d(np.asarray(theta, dtype=np.float64))
+    ok = np.ones(theta.shape[0], dtype=bool)
+    if not len(ma_lags):
+        return ok
+    L = int(max(ma_lags))
+    full = np.zeros((theta.shape[0], L))
+    full[:, np.asarray(ma_lags) - 1] = theta
+    rows = np.isfinite(full).all(axis=1)
+    comp = np.zeros((int(rows.sum()), L, L))
+    comp[:, 0, :] = -full[rows]
+    comp[:, np.arange(1, L), np.arange(L - 1)] = 1.0
+    if comp.shape[0]:
+        ok[rows] = np.abs(np.linalg.eigvals(comp)).max(axis=1) < 1.0
+    return ok
+
+
+def _lag_array(lags):
+    return (C.c_int32 * 12)(*[int(v) for v in lags])
+
+
+class SarimaBaseline:
+    """The reference's `SarimaBaseline(order, seasonal_order)` with `fit` and `predict`, fitted and forecast on the device
+    (see the module docstring for the estimator and how it differs from statsmodels').  After `fit`: `ar_lags`,
+    `ma_lags`, `coef_` (N, K) = (phi over ar_lags, theta over ma_lags), `sigma2_` (N), `status_` (N) int32 with the bits
+    `DEGENERATE` (zero coefficients: the forecast is the differencing rule alone), `NONFINITE` (NaN coefficients) and
+    `MA_DROPPED` (the fitted theta was not invertible; the node was solved again as a pure AR) -- numpy arrays all."""
+    DEGENERATE, NONFINITE, MA_DROPPED = _lib.TECM_SAR_DEGENERATE, _lib.TECM_SAR_NONFINITE, _lib.TECM_SAR_MA_DROPPED
+    PREDICT_WINDOW = 1024
+
+    def __init__(self, order=(1, 1, 1), seasonal_order=(1, 1, 1, 12), long_ar=None, device: Union[str, torch.device] = "cuda"):
+        self.d, self.D, self.s, ar, ma, self.long_ar = sarima_lags(order, seasonal_order, long_ar)
+        self.order, self.seasonal_order = tuple(order), tuple(seasonal_order)
+        self.ar_lags, self.ma_lags = np.asarray(ar, dtype=np.int32), np.asarray(ma, dtype=np.int32)
+        self.device = torch.device(device)
+        self.coef_ = self.sigma2_ = self.status_ = self.autocov_ = self.nodes_ = self.tail_ = None
+        self._coef_dev = None
+
+    # joblib / pickle: numpy only
+    def __getstate__(self):
+        state = {k: v for k, v in self.__dict__.items() if k != "_coef_dev"}
+        state["device"] = str(self.device)
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.device, self._coef_dev = torch.device(state["device"]), None
+
+    @property
+    def K(self) -> int:
+        return len(self.ar_lags) + len(self.ma_lags)
+
+    @property
+    def lmax(self) -> int:
+        return int(max(list(self.ar_lags) + list(self.ma_lags)))
+
+    @property
+    def offset(self) -> int:
+        return self.d + self.s * self.D
+
+    def _fit_desc(self, series, out, use_ma=None, ws=None) -> TecmSarFit:
+        return TecmSarFit(x=series.data_ptr(), stride_t=series.stride(0), stride_n=series.stride(1), T=series.shape[0],
+                          N=series.shape[1], d=self.d, D=self.D, s=self.s, m=self.long_ar, n_ar=len(self.ar_lags),
+                          n_ma=len(self.ma_lags), ar_lags=_lag_array(self.ar_lags), ma_lags=_lag_array(self.ma_lags),
+                          autocov=out["autocov"].data_ptr(), gram=out["gram"].data_ptr(), wss=out["wss"].data_ptr(),
+                          coef=out["coef"].data_ptr(), sigma2=out["sigma2"].data_ptr(), status=out["status"].data_ptr(),
+                          use_ma=None if use_ma is None else use_ma.data_ptr(), ws=None if ws is None else ws.data_ptr())
+
+    def fit_device(self, series: torch.Tensor):
+        """Stage 1 and 2 on a (T, N) float32 device tensor of any non-negative strides: a dict of device tensors `autocov`
+        (N, m+1), `gram` (N, K, K+1), `wss` (N), `coef` (N, K), `sigma2` (N), all float64, and `status` (N) int32 --
+        what `tecm_sar_fit` writes, before the invertibility repair of `fit`."""
+        require_gpu_tensor(series, "series")
+        if series.dim() != 2:
+            raise ValueError(f"series must be (T, N), got {tuple(series.shape)}")
+        N, K, f64 = series.shape[1], self.K, dict(device=series.device, dtype=torch.float64)
+        out = {"autocov": torch.empty(N, self.long_ar + 1, **f64), "gram": torch.empty(N, K, K + 1, **f64),
+               "wss": torch.empty(N, **f64), "coef": torch.empty(N, K, **f64), "sigma2": torch.empty(N, **f64),
+               "status": torch.empty(N, device=series.device, dtype=torch.int32)}
+        desc = self._fit_desc(series, out)
+        nbytes = lib().tecm_sar_fit_ws_bytes(C.byref(desc))
+        if nbytes < 0:
+            check(1, "tecm_sar_fit_ws_bytes")
+        ws = torch.empty(nbytes // 8, **f64)
+        desc = self._fit_desc(series, out, ws=ws)
+        check(lib().tecm_sar_fit(C.byref(desc), stream_ptr()), "tecm_sar_fit")
+        return out
+
+    def solve_device(self, series: torch.Tensor, out, use_ma: torch.Tensor) -> None:
+        """Solves the nodes with `use_ma[node] == 0` again from `out["gram"]` as pure AR models (theta = 0), in place."""
+        require_gpu_tensor(use_ma, "use_ma", torch.int8)
+        if use_ma.shape != (series.shape[1],):
+            raise ValueError(f"use_ma must hold one flag per node ({series.shape[1]})")
+        desc = self._fit_desc(series, out, use_ma=use_ma.contiguous())
+        check(lib().tecm_sar_solve(C.byref(desc), stream_ptr()), "tecm_sar_solve")
+
+    def fit(self, tec_data: ArrayLike, node_indices=None) -> "SarimaBaseline":
+        """tec_data (N_times, N_nodes): a numpy array (uploaded once) or a device tensor (read in place, e.g. channel 0 of
+        a resident split).  `node_indices` None fits every node; a list fits those columns only, as the reference does.
+        One host synchronisation: theta is checked for invertibility with numpy and the nodes that fail are solved
+        again without their MA part (`MA_DROPPED`)."""
+        series = tec_data if isinstance(tec_data, torch.Tensor) else torch.as_tensor(np.asarray(tec_data))
+        series = series.to(device=self.device if not series.is_cuda else series.device, dtype=torch.float32)
+        if series.dim() != 2:
+            raise ValueError(f"tec_data must be (N_times, N_nodes), got {tuple(series.shape)}")
+        if node_indices is None:
+            nodes = np.arange(series.shape[1], dtype=np.int64)
+        else:
+            nodes = np.asarray([int(i) for i in node_indices], dtype=np.int64)
+            series = series.index_select(1, torch.as_tensor(nodes).to(series.device))
+        log.info("Fitting SARIMA (Hannan-Rissanen) for %d nodes...", len(nodes))
+        out = self.fit_device(series)
+        n_ar = len(self.ar_lags)
+        theta = out["coef"][:, n_ar:].cpu().numpy()
+        bad = ~ma_invertible(theta, self.ma_lags)
+        if bad.any():
+            use_ma = torch.as_tensor((~bad).astype(np.int8)).to(series.device)
+            self.solve_device(series, out, use_ma)
+        self._coef_dev = out["coef"]
+        self.coef_, self.sigma2_ = out["coef"].cpu().numpy(), out["sigma2"].cpu().numpy()
+        self.status_, self.autocov_ = out["status"].cpu().numpy(), out["autocov"].cpu().numpy()
+        self.nodes_ = nodes
+        self.tail_ = series[-min(series.shape[0], self.PREDICT_WINDOW):].contiguous().cpu().numpy()
+        log.info("SARIMA fitted: %d degenerate, %d non-finite, %d without MA part.", int((self.status_ & 1 != 0).sum()),
+                 int((self.status_ & 2 != 0).sum()), int((self.status_ & 4 != 0).sum()))
+        return self
+
+    def _coef_on(self, device) -> torch.Tensor:
+        if self.coef_ is None:
+            raise ValueError("SarimaBaseline used before fit()")
+        if self._coef_dev is None or self._coef_dev.device != device:
+            self._coef_dev = torch.as_tensor(self.coef_).to(device).contiguous()
+        return self._coef_dev
+
+    def forecast_series(self, X: torch.Tensor, starts: Sequence[int], L_in: int, L_out: int, channel: int = 0,
+                        out: torch.Tensor = None, coef: torch.Tensor = None, host_check: bool = True) -> torch.Tensor:
+        """Forecasts from the windows X[a : a + L_in, :, channel], a in `starts`, of a (T, N, C) float32 device tensor:
+        (B, L_out, N) float32, or written into `out` (any strides).  `coef` (N, K) float64 on the device replaces the
+        fitted coefficients.  Without `host_check` a window outside [0, T - L_in] reaches the kernel, which writes NaN."""
+        require_gpu_tensor(X, "X")
+        if X.dim() != 3 or not X.is_contiguous():
+            raise ValueError(f"X must be a contiguous (T, N, C) tensor, got {tuple(X.shape)}")
+        T, N, Cc = X.shape
+        need = self.offset + self.lmax + 1
+        if L_in < need:
+            raise ValueError(f"L_in = {L_in} is shorter than d + s D + Lmax + 1 = {need}")
+        coef = self._coef_on(X.device) if coef is None else coef
+        require_gpu_tensor(coef, "coef", torch.float64)
+        if coef.shape != (N, self.K) or not coef.is_contiguous():
+            raise ValueError(f"coefficients of shape {tuple(coef.shape)} do not fit {N} nodes x {self.K} lags")
+        host = torch.tensor([int(a) for a in starts], dtype=torch.int64)
+        B = host.numel()
+        if B == 0:
+            raise ValueError("forecast_series() needs at least one window")
+        if out is None:
+            out = torch.empty(B, int(L_out), N, device=X.device, dtype=torch.float32)
+        require_gpu_tensor(out, "out")
+        if out.shape != (B, int(L_out), N):
+            raise ValueError(f"out must be {(B, int(L_out), N)}, got {tuple(out.shape)}")
+        dev_starts = host.to(X.device, non_blocking=True)
+        w = TecmWindowBaseline(X=X.data_ptr(), starts=dev_starts.data_ptr(), starts_host_check=host.data_ptr() if host_check else None, T=T, N=N,
+                               C=Cc, channel=int(channel), L_in=int(L_in), L_out=int(L_out), B=B, mode=0, period=0,
+                               out=out.data_ptr(), o_stride_b=out.stride(0), o_stride_h=out.stride(1) if L_out > 1 else 1,
+                               o_stride_n=out.stride(2))
+        f = TecmSarForecast(w=w, coef=coef.data_ptr(), d=self.d, D=self.D, s=self.s, n_ar=len(self.ar_lags),
+                            n_ma=len(self.ma_lags), ar_lags=_lag_array(self.ar_lags), ma_lags=_lag_array(self.ma_lags))
+        check(lib().tecm_sar_forecast(C.byref(f), stream_ptr()), "tecm_sar_forecast")
+        return out
+
+    def forecast_windows(self, dataset, indices: Sequence[int], channel: int = 0) -> torch.Tensor:
+        """Forecasts for the windows `indices` of a `SlidingWindowSamplerDataset` as a (B, L_out, N, 1) device tensor, the
+        layout of the model's output: one launch for any number of windows.  Reads `channel` of the feature-scaled X as
+        it is, like the other baselines of `tecmollm.evaluate`.  The model must have been fitted on every node."""
+        idx = [int(i) for i in indices]
+        for i in idx:
+            if not 0 <= i < dataset.num_samples:
+                raise IndexError(f"Index {i} is out of bounds for a dataset of size {dataset.num_samples}")
+        T, H, W, Cc = dataset.X.shape
+        starts = [dataset.sample_indices[i] for i in idx]
+        out = self.forecast_series(dataset.X.view(T, H * W, Cc), starts, dataset.L_in, dataset.L_out, channel)
+        return out.unsqueeze(-1)
+
+    def predict(self, node_indices, steps: int) -> dict:
+        """{node: (steps,) float64} for the fitted nodes among `node_indices`: the forecast from the end of the training
+        series, whose last min(T, 1024) steps are the window."""
+        if self.coef_ is None:
+            raise ValueError("SarimaBaseline.predict() before fit()")
+        tail = torch.as_tensor(self.tail_).to(self.device).unsqueeze(-1).contiguous()
+        out = self.forecast_series(tail, [0], tail.shape[0], int(steps)).cpu().numpy().astype(np.float64)
+        col = {int(n): j for j, n in enumerate(self.nodes_)}
+        return {int(n): out[0, :, col[int(n)]] for n in node_indices if int(n) in col}
 
 
 def save_baseline(model, path):

@@ -176,6 +176,27 @@ class TecmSlotMean(C.Structure):
     ]
 
 
+class TecmSarFit(C.Structure):
+    _fields_ = [
+        ("x", c_f32p), ("stride_t", C.c_int64), ("stride_n", C.c_int64),
+        ("T", C.c_int64),
+        ("N", C.c_int32), ("d", C.c_int32), ("D", C.c_int32), ("s", C.c_int32), ("m", C.c_int32), ("n_ar", C.c_int32),
+        ("n_ma", C.c_int32), ("_pad", C.c_int32),
+        ("ar_lags", C.c_int32 * 12), ("ma_lags", C.c_int32 * 12),
+        ("autocov", C.c_void_p), ("gram", C.c_void_p), ("wss", C.c_void_p), ("coef", C.c_void_p), ("sigma2", C.c_void_p),
+        ("status", C.c_void_p), ("use_ma", C.c_void_p), ("ws", C.c_void_p),
+    ]
+
+
+class TecmSarForecast(C.Structure):
+    _fields_ = [
+        ("w", TecmWindowBaseline),
+        ("coef", C.c_void_p),
+        ("d", C.c_int32), ("D", C.c_int32), ("s", C.c_int32), ("n_ar", C.c_int32), ("n_ma", C.c_int32), ("_pad", C.c_int32),
+        ("ar_lags", C.c_int32 * 12), ("ma_lags", C.c_int32 * 12),
+    ]
+
+
 class TecmConvDx(C.Structure):
     _fields_ = [("dy", C.c_void_p), ("wpack", C.c_void_p), ("dinp", c_f32p),
                 ("B", C.c_int32), ("Lc", C.c_int32), ("N", C.c_int32), ("Cout", C.c_int32), ("ld_in", C.c_int32),
@@ -202,6 +223,8 @@ TECM_ENS_STATS = 9
 TECM_ENS_MAX_K = 64
 TECM_ATTN_SKIP_UNCONNECTED = 1
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
+TECM_SAR_MAX_K, TECM_SAR_MAX_LAG, TECM_SAR_MAX_LONG_AR, TECM_SAR_MAX_OFFSET, TECM_SAR_CHUNK = 12, 32, 64, 64, 1024
+TECM_SAR_DEGENERATE, TECM_SAR_NONFINITE, TECM_SAR_MA_DROPPED = 1, 2, 4
 
 
 EXPORTS = {
@@ -291,6 +314,10 @@ EXPORTS = {
     "tecm_window_batch": (C.c_int, [C.POINTER(TecmWindowBatch), C.c_void_p]),
     "tecm_window_baseline": (C.c_int, [C.POINTER(TecmWindowBaseline), C.c_void_p]),
     "tecm_slot_mean": (C.c_int, [C.POINTER(TecmSlotMean), C.c_void_p]),
+    "tecm_sar_fit_ws_bytes": (C.c_int64, [C.POINTER(TecmSarFit)]),
+    "tecm_sar_fit": (C.c_int, [C.POINTER(TecmSarFit), C.c_void_p]),
+    "tecm_sar_solve": (C.c_int, [C.POINTER(TecmSarFit), C.c_void_p]),
+    "tecm_sar_forecast": (C.c_int, [C.POINTER(TecmSarForecast), C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -35,6 +35,26 @@ KINDS = {"mean": _lib.TECM_BASELINE_MEAN, "last": _lib.TECM_BASELINE_LAST, "peri
 # result-dict names: "HistoricalAverage" is the reference's (test.py:217); the other two are not in the reference
 NAMES = {"mean": "HistoricalAverage", "last": "Persistence", "periodic": "DayAgo"}
 MODEL_NAME = "TEC-MoLLM"
+SARIMA_NAME = "SARIMA"      # a fitted src.models.baselines.SarimaBaseline given as an element of `baselines=`
+
+
+def baseline_name(kind) -> str:
+    """The result-dict name of one element of `baselines=`: a kind string of `KINDS`, or a fitted `SarimaBaseline`."""
+    if isinstance(kind, str):
+        if kind in KINDS:
+            return NAMES[kind]
+    else:
+        from src.models.baselines import SarimaBaseline
+        if isinstance(kind, SarimaBaseline):
+            if kind.coef_ is None:
+                raise ValueError("a SarimaBaseline given as a baseline must be fitted")
+            return SARIMA_NAME
+    raise ValueError(f"baselines must come from {sorted(KINDS)}, got {kind!r}")
+
+
+def baseline_forecast(dataset, indices: Sequence[int], kind) -> torch.Tensor:
+    """The (B, L_out, N, 1) forecast of one element of `baselines=` for the windows `indices`."""
+    return window_baseline(dataset, indices, kind) if isinstance(kind, str) else kind.forecast_windows(dataset, indices)
 
 
 def _launch(dataset, indices: Sequence[int], kind: str, channel: int, period: int, L_out: int, out: torch.Tensor,
@@ -98,9 +118,7 @@ def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_
     of its own and, when `num_groups` is given, a `MapMetrics` too.  Returns ({name: HorizonMetrics}, {name: MapMetrics})."""
     from src.evaluation.metrics import HorizonMetrics, MapMetrics
     kinds = list(baselines)
-    for k in kinds:
-        if k not in KINDS:
-            raise ValueError(f"baselines must come from {sorted(KINDS)}, got {k!r}")
+    names = [baseline_name(k) for k in kinds]
     model.eval()
     hms: Dict[str, HorizonMetrics] = {}
     mms: Dict[str, MapMetrics] = {}
@@ -108,14 +126,14 @@ def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_
         x, tf, y = dataset.batch(chunk)
         out = model(x, tf, edge_index, edge_weight)
         if not hms:
-            for name in [MODEL_NAME] + [NAMES[k] for k in kinds]:
+            for name in [MODEL_NAME] + names:
                 hms[name] = HorizonMetrics(out.shape[1], scaler, device=out.device)
                 if num_groups is not None:
                     mms[name] = MapMetrics(out.shape[1], out.shape[2], num_groups, scaler, device=out.device)
         ids = None
         if mms and groups is not None:
             ids = groups[torch.as_tensor(chunk, dtype=torch.int64).to(groups.device, non_blocking=True)]
-        forecasts = [(MODEL_NAME, out)] + [(NAMES[k], window_baseline(dataset, chunk, k)) for k in kinds]
+        forecasts = [(MODEL_NAME, out)] + [(name, baseline_forecast(dataset, chunk, k)) for name, k in zip(names, kinds)]
         for name, pred in forecasts:
             hms[name].update(pred, y)
             if mms:
@@ -131,7 +149,9 @@ def evaluate_split(model: torch.nn.Module, dataset, edge_index: torch.Tensor, ba
     `evaluate_horizons` dict of that forecast against the split's targets.
 
     One pass over the batches: the model's output and each baseline's stride-0 view are fed in place to a
-    `HorizonMetrics` of their own, with no host synchronisation per batch.  `order` and `group` as in `loop.validate`:
+    `HorizonMetrics` of their own, with no host synchronisation per batch.  An element of `baselines` is a kind string of
+    `window_baseline` or a fitted `src.models.baselines.SarimaBaseline`, whose entry is named "SARIMA" (one
+    `tecm_sar_forecast` launch per batch); the same holds for `evaluate_maps` and `evaluate_ensemble`.  `order` and `group` as in `loop.validate`:
     a rank evaluates its shard and every rank returns the metrics of the whole split."""
     hms, _ = _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_weight, order, None, None)
     if not hms:

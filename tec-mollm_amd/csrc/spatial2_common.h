@@ -3,7 +3,7 @@
 //     x_m[g, n] = A_m x[g, n] + P_m[n] + c_m(g),   A_m = W_m[:, :Cin],  P_m[n] = W_m[:, Cin:] node_emb[n],
 //                                                  c_m(g) = W_m[:, Cin:] temb_g + b_m
 #pragma once
-#include "spatial_common.h"
+#include "spatial_edge.h"
 
 namespace tecm_spatial2 {
 using namespace tecm_spatial;

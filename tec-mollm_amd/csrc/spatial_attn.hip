@@ -23,15 +23,12 @@
 //               m (entropy) to the fp64 statistics of the graph's group with plain loads and stores -- one owner per cell,
 //               so the same calls give the same bits, whatever the chunking.
 // The workspace holds one chunk of graphs (<= 64 MiB unless one graph needs more), the launcher walks the chunks.
-#include "spatial_common.h"
+// The logit, the row loads and the graph decode are spatial_edge.h's, shared with the other spatial kernels.
+#include "spatial_edge.h"
 
 using namespace tecm_spatial;
 
 namespace {
-
-constexpr int TB = 256;                 // threads of a block
-constexpr int HP = 12;                  // floats per head in a workspace row: 11 channels | norm (x_l) or pad (x_r)
-constexpr int64_t WS_CHUNK_BYTES = (int64_t)64 << 20;
 
 struct AttnArgs {
   TecmSpatial d;
@@ -55,16 +52,11 @@ __host__ __device__ inline WsLayout ws_layout(const AttnArgs& q) {
   return w;
 }
 
-// one head of a workspace row (16-byte aligned): 11 channels and the float behind them
-__device__ __forceinline__ float ld11(const float* p, float (&v)[CH]) {
-  const float4* q = reinterpret_cast<const float4*>(p);
-  const float4 a = q[0], b = q[1], c = q[2];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  v[8] = c.x; v[9] = c.y; v[10] = c.z;
-  return c.w;
-}
-
-// ---- rows: x_l (blockIdx.y == 0) or x_r (1) of 256 rows of the chunk
+// ---- rows: x_l (blockIdx.y == 0) or x_r (1) of 256 rows of the chunk.  spatial_dx_rows_kernel's transform plus the head
+//      norms, restated here: as two entry points of one __device__ body (norms behind a template flag) the compiler packs
+//      fewer of this kernel's FMAs (240 v_pk_fma_f32 + 48 v_fmac_f32 per row instead of 264 + 0) and the kernel measured
+//      slower at B = 8, L = 48, N = 2911: <10> 194.7 -> 202.1 us per update (parent spread 0.3), spatial_dx_rows_kernel<10>
+//      360.5 -> 364.5 us (spread 3.9); profiles/spatial_shared_math.txt.
 template <int CIN>
 __global__ __launch_bounds__(TB) void spatial_attn_rows_kernel(const AttnArgs a) {
   constexpr int DEMB = C - CIN;
@@ -91,8 +83,8 @@ __global__ __launch_bounds__(TB) void spatial_attn_rows_kernel(const AttnArgs a)
     h[2 * k + 1] = v.y;
   }
   if constexpr (DEMB > 0) {
-    const int b = gm / d.L, t = gm - b * d.L;
-    const TimeIdx ti = load_time_idx(d, b, t, node);
+    const Graph g = decode_graph(d, gm);
+    const TimeIdx ti = load_time_idx(d, g.b, g.t, node);
 #pragma unroll
     for (int e = 0; e < DEMB; ++e) h[CIN + e] = d.node_tab[(int64_t)node * DEMB + e] + temporal_emb(d, ti, e);
   }
@@ -135,8 +127,7 @@ __global__ __launch_bounds__(TB) void spatial_attn_target_kernel(const AttnArgs 
   if ((idx >> 1) >= rows) return;
   const int hh = idx & 1, r = idx >> 1;
   const int gl = r / d.N, i = r - gl * d.N, gm = a.g0 + gl;
-  const int b = gm / d.L, t = gm - b * d.L;
-  const bool use_edges = (t * d.B + b) < d.graphs_with_edges;         // the reference's flattening is (L*B): g = t*B + b
+  const bool use_edges = decode_graph(d, gm).use_edges;
   const int E1 = a.a.E, E2 = E1 + d.N;
   const bool acc = a.a.edge_stats != nullptr;
   const WsLayout w = ws_layout(a);
@@ -158,8 +149,8 @@ __global__ __launch_bounds__(TB) void spatial_attn_target_kernel(const AttnArgs 
       if (out && writable(p)) out[(int64_t)p * H] = 0.f;
     }
   }
-  float xr[CH], att[CH];
-  ld11(w.xr + (int64_t)r * CP + hh * HP, xr);
+  float xr[CH + 1], att[CH];
+  ld12(w.xr + (int64_t)r * CP + hh * HP, xr);
 #pragma unroll
   for (int c = 0; c < CH; ++c) att[c] = d.att[hh * CH + c];
   const float* xlg = w.xl + (int64_t)gl * d.N * CP + hh * HP;
@@ -170,13 +161,11 @@ __global__ __launch_bounds__(TB) void spatial_attn_target_kernel(const AttnArgs 
   float mx = -INFINITY;
   for (int s = 0; s <= deg; ++s) {
     const int j = s < deg ? d.colidx[e0 + s] : i, q = entry(s);
-    float al[CH];
-    const float nrm = ld11(xlg + (int64_t)j * CP, al);
-    float e = 0.f;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) e = fmaf(att[c], lrelu(al[c] + xr[c]), e);
+    float al[CH + 1];                                                 // al[CH]: the head's norm
+    ld12(xlg + (int64_t)j * CP, al);
+    const float e = logit_lrelu(al, xr, att);
     mx = fmaxf(mx, e);
-    if (acc) wms[(int64_t)q * H] = nrm;
+    if (acc) wms[(int64_t)q * H] = al[CH];
     if (acc || writable(place(q))) park[parked(q)] = e;
   }
   // sweep 2: the denominator, from the terms sweep 3 divides
@@ -246,13 +235,13 @@ __global__ __launch_bounds__(TB) void spatial_attn_accumulate_kernel(const AttnA
     for (int u = 0; u < U; ++u) {
       const int gl = gb + u;
       if (gl >= a.gc) break;
-      const int gm = a.g0 + gl, b = gm / d.L, t = gm - b * d.L;
+      const int gm = a.g0 + gl;
       const int g = s.group ? s.group[gm] : 0;
       if ((unsigned)g >= (unsigned)s.num_groups) {                    // skipped, never clamped
         bad = true;
         continue;
       }
-      if (skip && (t * d.B + b) >= d.graphs_with_edges) continue;
+      if (skip && !decode_graph(d, gm).use_edges) continue;
       if (g != cur) {                                                  // the running sums of a group live in registers
         flush();
         cur = g;

@@ -16,7 +16,9 @@
 //       cores (v_mfma_f32_16x16x4_f32, accumulators live in registers across all items of the block); the ones row
 //       yields the per-item column sums that the temporal tables need (d temb_g = sum_n d h[n, Cin:]).
 // The node table receives  sum_g d h[g, n, Cin:]  once per tile from register accumulators of d x_l, d x_r, dout.
-#include "spatial_common.h"
+// The per-edge arithmetic of B1 and B2 (logit with dalpha, online-softmax step, what de adds to d x_r / d att / d x_l, the
+// dropout mask index) is spatial_edge.h's, shared with spatial_bwd2.hip and spatial_dx.hip.
+#include "spatial_edge.h"
 
 using namespace tecm_spatial;
 
@@ -88,14 +90,6 @@ __device__ unsigned long long g_spb_stamps[16];
 #else
 #define SPB_T(slot) do {} while (0)
 #endif
-
-__device__ __forceinline__ f32x16 splat16(float v) {
-  f32x16 a;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) a[e] = v;
-  return a;
-}
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
 // value of the neighbouring lane (lane ^ 1) through DPP quad_perm [1,0,3,2]: no LDS, one instruction
 __device__ __forceinline__ float swap1(float v) {
@@ -259,21 +253,6 @@ __device__ __attribute__((noinline)) void bwd_node_table(const BwdArgs* ap, int 
   }
 }
 
-__device__ __forceinline__ void load12(const float* p, float (&v)[CH + 1]) {
-  const float4* q = reinterpret_cast<const float4*>(p);
-  const float4 a = q[0], b = q[1], c = q[2];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
-}
-__device__ __forceinline__ void store12(float* p, const float (&v)[CH], float last) {
-  float4* q = reinterpret_cast<float4*>(p);
-  q[0] = make_float4(v[0], v[1], v[2], v[3]);
-  q[1] = make_float4(v[4], v[5], v[6], v[7]);
-  q[2] = make_float4(v[8], v[9], v[10], last);
-}
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
 template <int SRC_R>
 __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -315,9 +294,8 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
   float att[CH];
 #pragma unroll
   for (int c = 0; c < CH; ++c) att[c] = smem[m.scr + SCR_ATT + hh * CH + c];
-  const uint32_t dth = d.alpha_drop.p > 0.f ? tecm_drop_thresh(d.alpha_drop.p) : 0u;
-  const float dinv = d.alpha_drop.p > 0.f ? 1.0f / (1.0f - d.alpha_drop.p) : 1.0f;
-  const uint64_t dseed = tecm_seed_now(d.alpha_drop.seed, d.alpha_drop.seed_dev);
+  const AlphaDrop dr = alpha_drop_of(d);
+  const uint64_t dseed = alpha_drop_seed(d);
   const bool even_cin = (Cin & 1) == 0;
   const unsigned cin_magic = (unsigned)((0x100000000ull + Cin - 1) / Cin);
 
@@ -360,7 +338,7 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
 #pragma unroll
     for (int r = 0; r < SRC_R; ++r) {
       const int w = sw + 256 * r;
-      if (w < W) store12(smem + m.xl + w * CP + hh * 12, DXL[r], 0.f);
+      if (w < W) st12(smem + m.xl + w * CP + hh * HP, DXL[r], 0.f);
 #pragma unroll
       for (int c = 0; c < CH; ++c) DXL[r][c] = 0.f;
     }
@@ -528,12 +506,11 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
     if (tgt) {
       const int wi = i - lo;
       float xr[CH + 1], gv[CH + 1];
-      load12(smem + m.xr + tn * CP + hh * 12, xr);
-      load12(smem + m.gt + tn * CP + hh * 12, gv);
+      ld12(smem + m.xr + tn * CP + hh * HP, xr);
+      ld12(smem + m.gt + tn * CP + hh * HP, gv);
       const int e0 = it.use_edges ? eptr[tn] : 0;
       const int deg = it.use_edges ? eptr[tn + 1] - e0 : 0;
-      const int64_t rowi = (int64_t)(it.t * d.B + it.b) * N + i;            // row in the reference's (L*B*N) flattening
-      const uint64_t dbase = (uint64_t)((rowi * H + hh) * d.alpha_drop.ld);
+      const uint64_t dbase = alpha_drop_base(d, (int64_t)(it.t * d.B + it.b) * N + i, hh);   // row of the (L*B*N) flattening
       const float base = (0.6f * LOG2E) * xr[CH];
       // de = alpha (dalpha - sum alpha dalpha) does not change when every dalpha of the target is shifted by one constant.
       // The self loop's dalpha (before dropout) is taken off: every rounding in sum alpha dalpha and in the products is
@@ -543,14 +520,8 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
       float da_ref;
       {
         float a[CH + 1];
-        load12(smem + m.xl + wi * CP + hh * 12, a);
-        float da = 0.f, db = 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          if (c & 1) db = fmaf(gv[c], a[c], db);
-          else da = fmaf(gv[c], a[c], da);
-        }
-        da_ref = da + db;
+        ld12(smem + m.xl + wi * CP + hh * HP, a);
+        da_ref = dot11_eo(gv, a);
       }
       // sweep 1: logits, dalpha, online softmax statistics over this lane's slots (slot deg = the implicit self loop)
       float mx = -INFINITY, z = 0.f, num = 0.f;
@@ -558,29 +529,13 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
         const int j = s < deg ? ecol[e0 + s] : wi;
         const int pos = s < deg ? e0 + s : E + tn;
         float a[CH + 1];
-        load12(smem + m.xl + j * CP + hh * 12, a);
-        // e = log2(e) * (0.6 (u_l + u_r) + 0.4 sum_c att_c |x_l[j,c] + x_r[i,c]|); even / odd channels in separate chains
-        float t0 = 0.f, u0 = 0.f, da = 0.f, db = 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          if (c & 1) {
-            u0 = fmaf(att[c], fabsf(a[c] + xr[c]), u0);
-            db = fmaf(gv[c], a[c], db);
-          } else {
-            t0 = fmaf(att[c], fabsf(a[c] + xr[c]), t0);
-            da = fmaf(gv[c], a[c], da);
-          }
-        }
-        const float e = fmaf(0.4f * LOG2E, t0 + u0, fmaf(0.6f * LOG2E, a[CH], base));
-        da += db;
-        if (dth) da *= tecm_drop_mult(dseed, dbase + s, dth, dinv);
+        ld12(smem + m.xl + j * CP + hh * HP, a);
+        float da;
+        const float e = logit_dalpha(a, xr, gv, att, base, da);
+        if (dr.th) da *= alpha_drop_mult(dr, dseed, dbase + s);
         da -= da_ref;
         *reinterpret_cast<float2*>(smem + m.ea + (pos * 2 + hh) * 2) = make_float2(e, da);
-        const float mn = fmaxf(mx, e);
-        const float corr = __builtin_amdgcn_exp2f(mx - mn), pw = __builtin_amdgcn_exp2f(e - mn);
-        z = z * corr + pw;
-        num = num * corr + pw * da;
-        mx = mn;
+        softmax_step(e, da, 1.0f, mx, z, num);
       }
       // pair combine: the even lane always owns slot 0, so the common maximum is finite
       const float mo = swap1(mx), zo = swap1(z), no = swap1(num);
@@ -597,30 +552,24 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
         float2* slot = reinterpret_cast<float2*>(smem + m.ea + (pos * 2 + hh) * 2);
         const float2 ed = *slot;                             // (e, dalpha * mult - da_ref)
         float a[CH + 1];
-        load12(smem + m.xl + j * CP + hh * 12, a);
+        ld12(smem + m.xl + j * CP + hh * HP, a);
         const float alpha = __builtin_amdgcn_exp2f(ed.x - mm) * zinv;
         float mult = 1.0f;
-        if (dth) mult = tecm_drop_mult(dseed, dbase + s, dth, dinv);
+        if (dr.th) mult = alpha_drop_mult(dr, dseed, dbase + s);
         const float de = alpha * (ed.y - dot);
         *slot = make_float2(alpha * mult, de);
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          const float sv = a[c] + xr[c];
-          const bool pos_ = sv > 0.f;
-          dxr[c] = fmaf(de, pos_ ? att[c] : NEG_SLOPE * att[c], dxr[c]);
-          datt[c] = fmaf(de, pos_ ? sv : NEG_SLOPE * sv, datt[c]);
-        }
+        de_to_dxr_datt(de, a, xr, att, dxr, datt);
       }
 #pragma unroll
       for (int c = 0; c < CH; ++c) dxr[c] += swap1(dxr[c]);  // both lanes now hold d x_r[i, head]
       if (sub == 0) {                                        // the tile's running sums (node-table gradient), in LDS
-        float4* rs = reinterpret_cast<float4*>(smem + m.rsum + tn * CP + hh * 12);
+        float4* rs = reinterpret_cast<float4*>(smem + m.rsum + tn * CP + hh * HP);
         float4 r0 = rs[0], r1 = rs[1], r2 = rs[2];
         r0.x += dxr[0]; r0.y += dxr[1]; r0.z += dxr[2]; r0.w += dxr[3]; r1.x += dxr[4]; r1.y += dxr[5];
         r1.z += dxr[6]; r1.w += dxr[7]; r2.x += dxr[8]; r2.y += dxr[9]; r2.z += dxr[10];
         rs[0] = r0; rs[1] = r1; rs[2] = r2;
         if (residual) {
-          float4* gs = reinterpret_cast<float4*>(smem + m.gsum + tn * CP + hh * 12);
+          float4* gs = reinterpret_cast<float4*>(smem + m.gsum + tn * CP + hh * HP);
           float4 g0 = gs[0], g1 = gs[1], g2 = gs[2];
           g0.x += gv[0]; g0.y += gv[1]; g0.z += gv[2]; g0.w += gv[3]; g1.x += gv[4]; g1.y += gv[5];
           g1.z += gv[6]; g1.w += gv[7]; g2.x += gv[8]; g2.y += gv[9]; g2.z += gv[10];
@@ -637,7 +586,7 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
       const int w = sw + 256 * r;                            // window row (the register sums DXL[r] belong to it)
       if (w >= wa && w < wb) {
         float xl[CH + 1], acc[CH];
-        load12(smem + m.xl + w * CP + hh * 12, xl);
+        ld12(smem + m.xl + w * CP + hh * HP, xl);
 #pragma unroll
         for (int c = 0; c < CH; ++c) acc[c] = 0.f;
         const bool self = w >= ta && w < tb;
@@ -649,22 +598,18 @@ __global__ __launch_bounds__(BT, 2) void spatial_bwd_kernel(const BwdArgs args) 
           const int tt = code >> 16;
           const float2 ad = *reinterpret_cast<const float2*>(smem + m.ea + ((code & 0xffff) * 2 + hh) * 2);   // (alpha~, de)
           float xr[CH + 1], gv[CH + 1];
-          load12(smem + m.xr + tt * CP + hh * 12, xr);
-          load12(smem + m.gt + tt * CP + hh * 12, gv);
-#pragma unroll
-          for (int c = 0; c < CH; ++c) {
-            const float sv = xl[c] + xr[c];
-            acc[c] = fmaf(ad.x, gv[c], fmaf(ad.y, sv > 0.f ? att[c] : NEG_SLOPE * att[c], acc[c]));
-          }
+          ld12(smem + m.xr + tt * CP + hh * HP, xr);
+          ld12(smem + m.gt + tt * CP + hh * HP, gv);
+          de_to_dxl(ad.x, ad.y, gv, xl, xr, att, acc);
         }
-        store12(smem + m.xl + w * CP + hh * 12, acc, 0.f);   // d x_l[w, head] replaces x_l (only this thread read it)
+        st12(smem + m.xl + w * CP + hh * HP, acc, 0.f);   // d x_l[w, head] replaces x_l (only this thread read it)
 #pragma unroll
         for (int c = 0; c < CH; ++c) DXL[r][c] += acc[c];
       }
     }
     __syncthreads();
     // d x_r from the B1 registers into the (now dead) x_r rows
-    if (tgt && sub == 0) store12(smem + m.xr + tn * CP + hh * 12, dxr, 0.f);
+    if (tgt && sub == 0) st12(smem + m.xr + tn * CP + hh * HP, dxr, 0.f);
     __syncthreads();
     SPB_T(4);
 

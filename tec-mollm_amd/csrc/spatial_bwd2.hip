@@ -27,6 +27,8 @@
 // Block end: node-embedding halves of dW_l / dW_r (one more outer-product pass over the register sums), node-table rows by
 // atomics, everything else into this block's row of `partials` in the first formulation's layout
 // [dWl (C*C) | dbl (C) | dWr (C*C) | dbr (C) | datt (C) | dbias (C, unused)] -- the caller's column sum is unchanged.
+// The per-edge arithmetic of B1 (logit with dalpha, what de adds to d x_r / d att, the dropout mask index) is spatial_edge.h's,
+// shared with spatial_bwd.hip; B2 keeps its own d x_l accumulation (see there).
 #include <cstdlib>
 #include "spatial2_common.h"
 
@@ -34,8 +36,6 @@ using namespace tecm_spatial;
 using namespace tecm_spatial2;
 
 namespace {
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
 
 struct Bwd2Args {
   TecmSpatial d;
@@ -45,20 +45,6 @@ struct Bwd2Args {
 };
 
 constexpr int PLD = 2 * C * C + 4 * C;
-
-__device__ __forceinline__ void ld12(const float* p, float (&v)[CH + 1]) {
-  const float4* q = reinterpret_cast<const float4*>(p);
-  const float4 a = q[0], b = q[1], c = q[2];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  v[8] = c.x; v[9] = c.y; v[10] = c.z; v[11] = c.w;
-}
-__device__ __forceinline__ void st12(float* p, const float (&v)[CH], float last) {
-  float4* q = reinterpret_cast<float4*>(p);
-  q[0] = make_float4(v[0], v[1], v[2], v[3]);
-  q[1] = make_float4(v[4], v[5], v[6], v[7]);
-  q[2] = make_float4(v[8], v[9], v[10], last);
-}
-__device__ __forceinline__ f32x4 zero4() { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 
 // LDS map (floats)
 struct Map2 {
@@ -128,9 +114,8 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
   float att[CH];
 #pragma unroll
   for (int c = 0; c < CH; ++c) att[c] = d.att[hh * CH + c];
-  const uint32_t dth = d.alpha_drop.p > 0.f ? tecm_drop_thresh(d.alpha_drop.p) : 0u;
-  const float dinv = d.alpha_drop.p > 0.f ? 1.0f / (1.0f - d.alpha_drop.p) : 1.0f;
-  const uint64_t dseed = tecm_seed_now(d.alpha_drop.seed, d.alpha_drop.seed_dev);
+  const AlphaDrop dr = alpha_drop_of(d);
+  const uint64_t dseed = alpha_drop_seed(d);
 
   // ---- sums that live across the block's graphs
   float SL[C], SR[CH], SG[CH], datt[CH];
@@ -164,8 +149,8 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
   };
   fetch_x(g0);
   for (int gm = g0; gm < g1; ++gm) {
-    const int b = gm / d.L, t = gm - b * d.L;
-    const bool use_edges = (t * d.B + b) < d.graphs_with_edges;
+    const Graph gq = decode_graph(d, gm);
+    const bool use_edges = gq.use_edges;
     const int wa = use_edges ? 0 : n0 - lo, wb = use_edges ? hi - lo : n1 - lo;
     const int64_t grow = (int64_t)gm * N;
     const float* __restrict__ gv = a.ws + ws_G(N) + (int64_t)gm * GV;
@@ -203,7 +188,7 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
 #pragma unroll
     for (int c = 0; c <= CH; ++c) xr[c] = gvv[c] = 0.f;
     if (tgt) {
-      ld12(R2 + tn * CP + hh * 12, xr);
+      ld12(R2 + tn * CP + hh * HP, xr);
       const float* gp = gr.dout + (grow + i) * CP + hh * CH;
 #pragma unroll
       for (int c = 0; c < CH; ++c) gvv[c] = gp[c];
@@ -214,22 +199,15 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
       const int e0 = te0;
       const int deg = use_edges ? tdeg : 0;
       const int* col = ecol + e0;
-      const int64_t rowi = (int64_t)(t * d.B + b) * N + i;   // row in the reference's (L*B*N) flattening
-      const uint64_t dbase = (uint64_t)((rowi * H + hh) * d.alpha_drop.ld);
+      const uint64_t dbase = alpha_drop_base(d, (int64_t)(gq.t * d.B + gq.b) * N + i, hh);   // row of the (L*B*N) flattening
       const float base = (0.6f * LOG2E) * xr[CH];
       // every dalpha of the target is shifted by the self loop's (csrc/spatial_bwd.hip, B1: de does not change, and its
       // roundings are relative to the spread of dalpha over the sources, not to a component common to all of them)
       float da_ref;
       {
         float al[CH + 1];
-        ld12(R1 + wi * CP + hh * 12, al);
-        float da = 0.f, db = 0.f;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          if (c & 1) db = fmaf(gvv[c], al[c], db);
-          else da = fmaf(gvv[c], al[c], da);
-        }
-        da_ref = da + db;
+        ld12(R1 + wi * CP + hh * HP, al);
+        da_ref = dot11_eo(gvv, al);
       }
       // sweep 1: logits, dalpha, online softmax statistics (slot deg = the implicit self loop), three slots per step: the
       // LDS round trips of a step overlap (col -> x_l row -> arithmetic is a dependent chain per slot)
@@ -244,21 +222,10 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
           const int j = sl < deg ? col[sl] : wi;
           const int pos = sl < deg ? e0 + sl : E + tn;
           float al[CH + 1];
-          ld12(R1 + j * CP + hh * 12, al);
-          float t0 = 0.f, u0 = 0.f, da = 0.f, db = 0.f;
-#pragma unroll
-          for (int c = 0; c < CH; ++c) {
-            if (c & 1) {
-              u0 = fmaf(att[c], fabsf(al[c] + xr[c]), u0);
-              db = fmaf(gvv[c], al[c], db);
-            } else {
-              t0 = fmaf(att[c], fabsf(al[c] + xr[c]), t0);
-              da = fmaf(gvv[c], al[c], da);
-            }
-          }
-          const float e = fmaf(0.4f * LOG2E, t0 + u0, fmaf(0.6f * LOG2E, al[CH], base));
-          da += db;
-          if (dth) da *= tecm_drop_mult(dseed, dbase + sl, dth, dinv);
+          ld12(R1 + j * CP + hh * HP, al);
+          float da;
+          const float e = logit_dalpha(al, xr, gvv, att, base, da);
+          if (dr.th) da *= alpha_drop_mult(dr, dseed, dbase + sl);
           da -= da_ref;
           if (valid) *reinterpret_cast<float2*>(R2 + (pos * 2 + hh) * 2) = make_float2(e, da);
           ev[u] = valid ? e : -INFINITY;
@@ -292,19 +259,13 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
           float2* slot = reinterpret_cast<float2*>(R2 + (pos * 2 + hh) * 2);
           const float2 ed = *slot;                           // (e, dalpha * mult - da_ref)
           float al[CH + 1];
-          ld12(R1 + j * CP + hh * 12, al);
+          ld12(R1 + j * CP + hh * HP, al);
           const float alpha = __builtin_amdgcn_exp2f(ed.x - mx) * zinv;
           float mult = 1.0f;
-          if (dth) mult = tecm_drop_mult(dseed, dbase + sl, dth, dinv);
+          if (dr.th) mult = alpha_drop_mult(dr, dseed, dbase + sl);
           const float de = valid ? alpha * (ed.y - dot) : 0.f;
           if (valid) *slot = make_float2(alpha * mult, de);
-#pragma unroll
-          for (int c = 0; c < CH; ++c) {
-            const float sv = al[c] + xr[c];
-            const bool pos_ = sv > 0.f;
-            dxr[c] = fmaf(de, pos_ ? att[c] : NEG_SLOPE * att[c], dxr[c]);
-            datt[c] = fmaf(de, pos_ ? sv : NEG_SLOPE * sv, datt[c]);
-          }
+          de_to_dxr_datt(de, al, xr, att, dxr, datt);
         }
       }
 #pragma unroll
@@ -334,11 +295,11 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
       float xr11[CH];
 #pragma unroll
       for (int c = 0; c < CH; ++c) xr11[c] = xr[c];
-      st12(R1 + tn * CP + hh * 12, xr11, 0.f);
+      st12(R1 + tn * CP + hh * HP, xr11, 0.f);
       float g11[CH];
 #pragma unroll
       for (int c = 0; c < CH; ++c) g11[c] = gvv[c];
-      st12(R1 + TN2 * CP + tn * CP + hh * 12, g11, 0.f);
+      st12(R1 + TN2 * CP + tn * CP + hh * HP, g11, 0.f);
     }
     __syncthreads();
 
@@ -360,12 +321,14 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
         for (int h2 = 0; h2 < H; ++h2) {
           if (h2) __builtin_amdgcn_sched_barrier(0);         // one head at a time: the two would double the live registers
           float xt[CH + 1], gt[CH + 1];
-          ld12(R1 + tt * CP + h2 * 12, xt);
-          ld12(R1 + TN2 * CP + tt * CP + h2 * 12, gt);
+          ld12(R1 + tt * CP + h2 * HP, xt);
+          ld12(R1 + TN2 * CP + tt * CP + h2 * HP, gt);
           const float al = h2 ? ad.z : ad.x, de = h2 ? ad.w : ad.y;
+          // de_to_dxl (spatial_edge.h) written out: through the helper this register-saturated kernel comes out of the
+          // compiler with more scratch (<10>: 148 -> 156 B per lane, 36 -> 40 spilled VGPRs; <6>: 124 -> 136 B, 33 -> 35)
 #pragma unroll
           for (int c = 0; c < CH; ++c) {
-            const float sv = xlw[h2 * 12 + c] + xt[c];
+            const float sv = xlw[h2 * HP + c] + xt[c];
             const float ac = d.att[h2 * CH + c];
             DXL[h2 * CH + c] = fmaf(al, gt[c], fmaf(de, sv > 0.f ? ac : NEG_SLOPE * ac, DXL[h2 * CH + c]));
           }
@@ -385,7 +348,7 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
       q[3] = make_float4(DXL[11], DXL[12], DXL[13], DXL[14]);
       q[4] = make_float4(DXL[15], DXL[16], DXL[17], DXL[18]);
       q[5] = make_float4(DXL[19], DXL[20], DXL[21], 0.f);
-      st12(R2 + tn * CP + hh * 12, dxr, 0.f);                // zeros for tn >= tile size
+      st12(R2 + tn * CP + hh * HP, dxr, 0.f);                // zeros for tn >= tile size
     }
     __syncthreads();
     if (!(SPB2_SKIP & 4)) {
@@ -459,7 +422,7 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
         v += __shfl_xor(v, 1);
         v += __shfl_xor(v, 2);
         if (p4 == 0) {
-        const TimeIdx ti = load_time_idx(d, b, t, 0);
+        const TimeIdx ti = load_time_idx(d, gq.b, gq.t, 0);
         atomicAdd(&gr.d_tod_tab[ti.tod * Demb + e], v);
         atomicAdd(&gr.d_doy_tab[ti.doy * Demb + e], v);
         atomicAdd(&gr.d_year_tab[ti.year * Demb + e], v);
@@ -480,7 +443,7 @@ __global__ __launch_bounds__(T2, SPB2_OCC) void spatial_bwd2_kernel(const Bwd2Ar
     q[3] = make_float4(SL[11], SL[12], SL[13], SL[14]);
     q[4] = make_float4(SL[15], SL[16], SL[17], SL[18]);
     q[5] = make_float4(SL[19], SL[20], SL[21], 0.f);
-    st12(R2 + tn * CP + hh * 12, SR, 0.f);
+    st12(R2 + tn * CP + hh * HP, SR, 0.f);
   }
   // node table: d node_emb[n][e] = sum_ch W_l[ch][Cin+e] S_l[n][ch]  (window rows)
   //                              + sum_ch W_r[ch][Cin+e] S_r[n][ch] + sum_g dout[g, n, Cin+e]  (tile rows, per head)

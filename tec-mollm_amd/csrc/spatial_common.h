@@ -92,20 +92,29 @@ __device__ __forceinline__ void store_head(float* row, int hh, const float (&v)[
   for (int c = 0; c < CH; ++c) p[c] = v[c];
 }
 
+// A graph number in the memory order of the (B, L, N, *) tensors, gm = b*L + t, taken apart.  The reference's flattening
+// is (L*B): g = t*B + b, and graphs g >= graphs_with_edges see only their self loops.
+struct Graph {
+  int b, t;
+  bool use_edges;
+};
+__device__ __forceinline__ Graph decode_graph(const TecmSpatial& d, int gm) {
+  Graph q;
+  q.b = gm / d.L;
+  q.t = gm - q.b * d.L;
+  q.use_edges = (q.t * d.B + q.b) < d.graphs_with_edges;
+  return q;
+}
 // One work item = (tile of target nodes, graph (b, t)).  Items are numbered tile-major so that a block's contiguous
 // range keeps its tile (CSR slice, node-embedding rows) across most of its items.
-struct Item {
-  int tile, b, t;
-  bool use_edges;
+struct Item : Graph {
+  int tile;
 };
 __device__ __forceinline__ Item decode_item(const TecmSpatial& d, int item) {
   const int G = d.B * d.L;
   Item it;
   it.tile = item / G;
-  const int gm = item - it.tile * G;           // memory order of the (B, L, N, *) tensors: gm = b*L + t
-  it.b = gm / d.L;
-  it.t = gm - it.b * d.L;
-  it.use_edges = (it.t * d.B + it.b) < d.graphs_with_edges;   // the reference's flattening is (L*B): g = t*B + b
+  static_cast<Graph&>(it) = decode_graph(d, item - it.tile * G);
   return it;
 }
 

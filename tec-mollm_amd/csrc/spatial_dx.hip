@@ -17,44 +17,24 @@
 //           and its slot in the target's list, so the dropout index is the forward's), recomputes e, alpha, mult and de from
 //           the statistics, sums d x_l[j] and adds W_l[:, :Cin]^T d x_l[j] to dx_j -- one writer per row.
 // In a graph without edges (graphs_with_edges) only the self loop is swept, at slot 0: alpha = 1, de = 0.
+// The logit, the online-softmax step, the de accumulations and the dropout mask index are spatial_edge.h's; the rows kernel
+// is restated in spatial_attn.hip (see there for why the two do not share one body).
 // The workspace holds one chunk of graphs (<= 64 MiB), the launcher walks the chunks.
 #include <cstdlib>
-#include "spatial_common.h"
+#include "spatial_edge.h"
 
 using namespace tecm_spatial;
 
 namespace {
 
-constexpr int TB = 256;                 // threads of a block
-constexpr int HP = 12;                  // floats per head in a workspace row: 11 channels | pad
 constexpr int SW = 8;                   // statistics per row: per head (max, 1 / denominator, sum alpha dalpha, pad)
 constexpr int WS_ROW = 2 * CP + SW;     // workspace floats per row: x_l | x_r | statistics
-constexpr int64_t WS_CHUNK_BYTES = (int64_t)64 << 20;
 
 struct DxArgs {
   TecmSpatial d;
   TecmSpatialDx g;
   int g0, gc;                           // graphs [g0, g0 + gc) in memory order gm = b*L + t
 };
-
-__device__ __forceinline__ void ld11(const float* p, float (&v)[CH]) {   // one head of a workspace row (16-byte aligned)
-  const float4* q = reinterpret_cast<const float4*>(p);
-  const float4 a = q[0], b = q[1], c = q[2];
-  v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-  v[8] = c.x; v[9] = c.y; v[10] = c.z;
-}
-__device__ __forceinline__ float logit(const float (&xl)[CH], const float (&xr)[CH], const float (&att)[CH]) {
-  float e = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) e = fmaf(att[c], lrelu(xl[c] + xr[c]), e);
-  return e;
-}
-__device__ __forceinline__ float dot11(const float (&a)[CH], const float (&b)[CH]) {
-  float v = 0.f;
-#pragma unroll
-  for (int c = 0; c < CH; ++c) v = fmaf(a[c], b[c], v);
-  return v;
-}
 
 // what a (row, head) thread of the target / source kernels knows about itself
 struct RowId {
@@ -74,10 +54,10 @@ __device__ __forceinline__ RowId row_id(const DxArgs& a) {
   const int gl = q.r / d.N, gm = a.g0 + gl;
   q.node = q.r - gl * d.N;
   q.rowbase = gl * d.N;
-  const int b = gm / d.L, t = gm - b * d.L;
+  const Graph g = decode_graph(d, gm);
   q.grow = (int64_t)gm * d.N;
-  q.mrow = (int64_t)(t * d.B + b) * d.N;
-  q.use_edges = (t * d.B + b) < d.graphs_with_edges;
+  q.mrow = (int64_t)(g.t * d.B + g.b) * d.N;
+  q.use_edges = g.use_edges;
   return q;
 }
 
@@ -98,7 +78,8 @@ __global__ __launch_bounds__(TB) void spatial_dx_rows_kernel(const DxArgs a) {
   const int rows = a.gc * d.N;
   const int r = blockIdx.x * TB + tid;
   if (r >= rows) return;
-  const int gl = r / d.N, node = r - gl * d.N, gm = a.g0 + gl, b = gm / d.L, t = gm - b * d.L;
+  const int gl = r / d.N, node = r - gl * d.N, gm = a.g0 + gl;
+  const Graph g = decode_graph(d, gm);
   float h[CP];
   const float2* xp = reinterpret_cast<const float2*>(d.x + ((int64_t)gm * d.N + node) * CIN);
 #pragma unroll
@@ -107,7 +88,7 @@ __global__ __launch_bounds__(TB) void spatial_dx_rows_kernel(const DxArgs a) {
     h[2 * k] = v.x;
     h[2 * k + 1] = v.y;
   }
-  const TimeIdx ti = load_time_idx(d, b, t, node);
+  const TimeIdx ti = load_time_idx(d, g.b, g.t, node);
 #pragma unroll
   for (int e = 0; e < DEMB; ++e) h[CIN + e] = d.node_tab[(int64_t)node * DEMB + e] + temporal_emb(d, ti, e);
   h[C] = h[C + 1] = 0.f;
@@ -163,8 +144,8 @@ __global__ __launch_bounds__(TB) void spatial_dx_target_kernel(const DxArgs a) {
   const float* __restrict__ XL = a.g.ws;
   const float* __restrict__ XR = a.g.ws + (int64_t)rows * CP;
   float* __restrict__ ST = a.g.ws + (int64_t)2 * rows * CP;
-  float xr[CH], gv[CH], att[CH], dxr[CH];
-  ld11(XR + (int64_t)q.r * CP + hh * HP, xr);
+  float xr[CH + 1], gv[CH], att[CH], dxr[CH];
+  ld12(XR + (int64_t)q.r * CP + hh * HP, xr);
   const float* gp = a.g.dout + (q.grow + i) * CP + hh * CH;
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
@@ -172,10 +153,9 @@ __global__ __launch_bounds__(TB) void spatial_dx_target_kernel(const DxArgs a) {
     att[c] = d.att[hh * CH + c];
     dxr[c] = 0.f;
   }
-  const uint32_t dth = d.alpha_drop.p > 0.f ? tecm_drop_thresh(d.alpha_drop.p) : 0u;
-  const float dinv = d.alpha_drop.p > 0.f ? 1.0f / (1.0f - d.alpha_drop.p) : 1.0f;
-  const uint64_t dseed = tecm_seed_now(d.alpha_drop.seed, d.alpha_drop.seed_dev);
-  const uint64_t dbase = (uint64_t)(((q.mrow + i) * H + hh) * d.alpha_drop.ld);
+  const AlphaDrop dr = alpha_drop_of(d);
+  const uint64_t dseed = alpha_drop_seed(d);
+  const uint64_t dbase = alpha_drop_base(d, q.mrow + i, hh);
   const int e0 = d.rowptr[i];
   const int deg = q.use_edges ? d.rowptr[i + 1] - e0 : 0;
   const float* xlg = XL + (int64_t)q.rowbase * CP + hh * HP;
@@ -183,30 +163,24 @@ __global__ __launch_bounds__(TB) void spatial_dx_target_kernel(const DxArgs a) {
   float mx = -INFINITY, z = 0.f, num = 0.f;
   for (int s = 0; s <= deg; ++s) {
     const int j = s < deg ? d.colidx[e0 + s] : i;
-    float al[CH];
-    ld11(xlg + (int64_t)j * CP, al);
-    const float e = logit(al, xr, att);
+    float al[CH + 1];
+    ld12(xlg + (int64_t)j * CP, al);
+    const float e = logit_lrelu(al, xr, att);
     float da = dot11(gv, al);
-    if (dth) da *= tecm_drop_mult(dseed, dbase + s, dth, dinv);
-    const float mn = fmaxf(mx, e);
-    const float corr = __builtin_amdgcn_exp2f((mx - mn) * LOG2E), pw = __builtin_amdgcn_exp2f((e - mn) * LOG2E);
-    z = fmaf(z, corr, pw);
-    num = fmaf(num, corr, pw * da);
-    mx = mn;
+    if (dr.th) da *= alpha_drop_mult(dr, dseed, dbase + s);
+    softmax_step(e, da, LOG2E, mx, z, num);
   }
   const float zinv = 1.0f / (z + 1e-16f);
   const float dot = num * zinv;
   // sweep 2: de per edge, d x_r
   for (int s = 0; s <= deg; ++s) {
     const int j = s < deg ? d.colidx[e0 + s] : i;
-    float al[CH];
-    ld11(xlg + (int64_t)j * CP, al);
-    const float e = logit(al, xr, att);
+    float al[CH + 1];
+    ld12(xlg + (int64_t)j * CP, al);
+    const float e = logit_lrelu(al, xr, att);
     float da = dot11(gv, al);
-    if (dth) da *= tecm_drop_mult(dseed, dbase + s, dth, dinv);
-    const float de = __builtin_amdgcn_exp2f((e - mx) * LOG2E) * zinv * (da - dot);
-#pragma unroll
-    for (int c = 0; c < CH; ++c) dxr[c] = fmaf(de, al[c] + xr[c] > 0.f ? att[c] : NEG_SLOPE * att[c], dxr[c]);
+    if (dr.th) da *= alpha_drop_mult(dr, dseed, dbase + s);
+    de_to_dxr(__builtin_amdgcn_exp2f((e - mx) * LOG2E) * zinv * (da - dot), al, xr, att, dxr);
   }
   float tot[CIN];
   to_input<CIN>(sWr, hh, dxr, tot);
@@ -231,36 +205,32 @@ __global__ __launch_bounds__(TB) void spatial_dx_source_kernel(const DxArgs a) {
   const float* __restrict__ XL = a.g.ws;
   const float* __restrict__ XR = a.g.ws + (int64_t)rows * CP;
   const float* __restrict__ ST = a.g.ws + (int64_t)2 * rows * CP;
-  float xl[CH], att[CH], dxl[CH];
-  ld11(XL + (int64_t)q.r * CP + hh * HP, xl);
+  float xl[CH + 1], att[CH], dxl[CH];
+  ld12(XL + (int64_t)q.r * CP + hh * HP, xl);
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
     att[c] = d.att[hh * CH + c];
     dxl[c] = 0.f;
   }
-  const uint32_t dth = d.alpha_drop.p > 0.f ? tecm_drop_thresh(d.alpha_drop.p) : 0u;
-  const float dinv = d.alpha_drop.p > 0.f ? 1.0f / (1.0f - d.alpha_drop.p) : 1.0f;
-  const uint64_t dseed = tecm_seed_now(d.alpha_drop.seed, d.alpha_drop.seed_dev);
+  const AlphaDrop dr = alpha_drop_of(d);
+  const uint64_t dseed = alpha_drop_seed(d);
   const int q0 = q.use_edges ? a.g.src_rowptr[j] : 0, q1 = q.use_edges ? a.g.src_rowptr[j + 1] : 0;
   const int self_slot = q.use_edges ? d.rowptr[j + 1] - d.rowptr[j] : 0;
   for (int p = q0; p <= q1; ++p) {                            // the out-edges of j in list order, then its self loop
     const int i = p < q1 ? a.g.src_target[p] : j;
     const int slot = p < q1 ? a.g.src_slot[p] : self_slot;
-    float xr[CH], gt[CH];
-    ld11(XR + (int64_t)(q.rowbase + i) * CP + hh * HP, xr);
+    float xr[CH + 1], gt[CH];
+    ld12(XR + (int64_t)(q.rowbase + i) * CP + hh * HP, xr);
     const float* gp = a.g.dout + (q.grow + i) * CP + hh * CH;
 #pragma unroll
     for (int c = 0; c < CH; ++c) gt[c] = gp[c];
     const float4 st = *reinterpret_cast<const float4*>(ST + ((int64_t)(q.rowbase + i) * 2 + hh) * 4);
-    const float e = logit(xl, xr, att);
+    const float e = logit_lrelu(xl, xr, att);
     float mult = 1.0f;
-    if (dth) mult = tecm_drop_mult(dseed, (uint64_t)(((q.mrow + i) * H + hh) * d.alpha_drop.ld) + slot, dth, dinv);
+    if (dr.th) mult = alpha_drop_mult(dr, dseed, alpha_drop_base(d, q.mrow + i, hh) + slot);
     const float alpha = __builtin_amdgcn_exp2f((e - st.x) * LOG2E) * st.y;
     const float de = alpha * (dot11(gt, xl) * mult - st.z);
-    const float am = alpha * mult;
-#pragma unroll
-    for (int c = 0; c < CH; ++c)
-      dxl[c] = fmaf(am, gt[c], fmaf(de, xl[c] + xr[c] > 0.f ? att[c] : NEG_SLOPE * att[c], dxl[c]));
+    de_to_dxl(alpha * mult, de, gt, xl, xr, att, dxl);
   }
   float tot[CIN];
   to_input<CIN>(sWl, hh, dxl, tot);

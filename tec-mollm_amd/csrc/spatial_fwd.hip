@@ -18,12 +18,12 @@
 //      hT[k][w] of the window (consecutive lanes = consecutive rows: conflict-free ds_read_b32), the bias enters as
 //      the accumulator's initial value;
 //   2. edges: one thread per (target node, head) -- all 256 threads busy, the head is wave-uniform -- walks the
-//      node's in-edges two at a time (two independent online-softmax chains, merged at the end), neighbour rows of
-//      x_l come from LDS; the result overwrites the thread's own x_r slice;
+//      node's in-edges four slots per online-softmax step (logit and step: spatial_edge.h, shared with
+//      spatial_fwd2.hip), neighbour rows of x_l come from LDS; the result overwrites the thread's own x_r slice;
 //   3. the output tile leaves through contiguous float4 stores.
 // Graphs with g = t*B + b >= graphs_with_edges see only their self loop (the reference's literal behaviour for
 // everything but graph 0); their window is the tile itself.
-#include "spatial_common.h"
+#include "spatial_edge.h"
 
 using namespace tecm_spatial;
 
@@ -60,13 +60,6 @@ __device__ unsigned long long g_spf_stamps[16];
 #ifndef SPF_SKIP
 #define SPF_SKIP 0     // diagnostic builds: bit0 no dense phase, bit1 no edge loop, bit2 no x prefetch
 #endif
-
-__device__ __forceinline__ f32x16 splat16(float v) {
-  f32x16 a;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) a[e] = v;
-  return a;
-}
 
 __device__ __forceinline__ const TecmSpatial* kernarg_desc() {
   return reinterpret_cast<const TecmSpatial*>(kernarg_base());
@@ -176,24 +169,19 @@ __device__ __attribute__((noinline)) void block_prologue(const TecmSpatial* dp, 
 }
 
 // Phase 2 for one head (compile time): online softmax over the in-edges + the implicit self loop, four slots per
-// step with ONE rescale of the accumulators per step; logits pre-scaled by log2(e) so the exponentials are bare
+// step (spatial_edge.h: logit_abs, softmax_step); logits pre-scaled by log2(e) so the exponentials are bare
 // v_exp_f32.  The result (residual + aggregate + bias) overwrites the thread's own x_r slice.
 template <int HH>
 __device__ __forceinline__ void edge_phase(const float* __restrict__ xg, int Cin, float* smem, int xl_off, int xr_off,
                                            int hT_off, int P, const int* eptr, const int* ecol, const float* temb,
                                            int tn, int wi, bool use_edges, uint64_t dseed, uint64_t dbase,
                                            const float (&att4)[CH], const float (&bias)[CH], bool residual,
-                                           bool tf_uniform, uint32_t dth, float dinv) {
+                                           bool tf_uniform, const AlphaDrop& dr) {
 #ifdef SPF_STAMPS
   unsigned long long estamp_ = __builtin_amdgcn_s_memtime();
 #endif
   float xr[CH + 1];                                          // xr[11] = u_r
-  {
-    const float4* p = reinterpret_cast<const float4*>(smem + xr_off + tn * CP + HH * 12);
-    const float4 a = p[0], b = p[1], c = p[2];
-    xr[0] = a.x; xr[1] = a.y; xr[2] = a.z; xr[3] = a.w; xr[4] = b.x; xr[5] = b.y; xr[6] = b.z; xr[7] = b.w;
-    xr[8] = c.x; xr[9] = c.y; xr[10] = c.z; xr[11] = c.w;
-  }
+  ld12(smem + xr_off + tn * CP + HH * HP, xr);
   float hres[CH];                                            // residual input h[i]: issued now, consumed at the very end
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
@@ -204,7 +192,7 @@ __device__ __forceinline__ void edge_phase(const float* __restrict__ xg, int Cin
   }
   const int e0 = use_edges ? eptr[tn] : 0;
   const int deg = use_edges ? eptr[tn + 1] - e0 : 0;
-  const float base = (0.6f * LOG2E) * xr[11];
+  const float base = (0.6f * LOG2E) * xr[CH];
   SPF_E(8);                                                  // x_r slice + degree
   float m = -INFINITY, z = 0.f;
   float acc[CH + 1];
@@ -216,44 +204,14 @@ __device__ __forceinline__ void edge_phase(const float* __restrict__ xg, int Cin
     for (int u = 0; u < 4; ++u) {
       const int sl = s + u;
       const int j = sl < deg ? ecol[e0 + sl] : wi;           // slots past the self loop re-read it and get weight 0
-      const float4* p = reinterpret_cast<const float4*>(smem + xl_off + j * CP + HH * 12);
-      const float4 q0 = p[0], q1 = p[1], q2 = p[2];
-      a[u][0] = q0.x; a[u][1] = q0.y; a[u][2] = q0.z; a[u][3] = q0.w; a[u][4] = q1.x; a[u][5] = q1.y;
-      a[u][6] = q1.z; a[u][7] = q1.w; a[u][8] = q2.x; a[u][9] = q2.y; a[u][10] = q2.z; a[u][11] = q2.w;
-      float e = fmaf(0.6f * LOG2E, q2.w, base);
-#pragma unroll
-      for (int c = 0; c + 1 < CH; c += 2) {                  // s = x_l[j] + x_r[i] two channels at a time (v_pk_add_f32)
-        const f32x2 sv = f32x2{a[u][c], a[u][c + 1]} + f32x2{xr[c], xr[c + 1]};
-        e = fmaf(att4[c], fabsf(sv.x), e);
-        e = fmaf(att4[c + 1], fabsf(sv.y), e);
-      }
-      e = fmaf(att4[CH - 1], fabsf(a[u][CH - 1] + xr[CH - 1]), e);
-      ev[u] = sl <= deg ? e : -INFINITY;
+      ld12(smem + xl_off + j * CP + HH * HP, a[u]);
+      ev[u] = sl <= deg ? logit_abs(a[u], xr, att4, base) : -INFINITY;
     }
-    const float mn = fmaxf(fmaxf(fmaxf(m, ev[0]), fmaxf(ev[1], ev[2])), ev[3]);   // slot s is always valid: mn is finite
-    const float corr = __builtin_amdgcn_exp2f(m - mn);       // exp2(-inf) = 0 on the first step
-    float pm[4], zs = 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const float p = __builtin_amdgcn_exp2f(ev[u] - mn);
-      zs += p;
-      pm[u] = p;
-      if (dth) pm[u] = p * tecm_drop_mult(dseed, dbase + s + u, dth, dinv);
-    }
-    z = z * corr + zs;
-    m = mn;
-#pragma unroll
-    for (int c = 0; c < CH + 1; c += 2) {                    // channel pairs (the 12th lane of the pair is the unused u)
-      f32x2 t = f32x2{acc[c], acc[c + 1]} * corr;
-#pragma unroll
-      for (int u = 0; u < 4; ++u) t = f32x2{a[u][c], a[u][c + 1]} * pm[u] + t;
-      acc[c] = t.x;
-      acc[c + 1] = t.y;
-    }
+    softmax_step<4>(a, ev, dr, dseed, dbase + s, m, z, acc);
   }
   SPF_E(9);                                                  // edge loop
   const float inv = 1.0f / (z + 1e-16f);
-  float* o = smem + xr_off + tn * CP + HH * 12;              // this thread's x_r slice is dead: it becomes the output
+  float* o = smem + xr_off + tn * CP + HH * HP;              // this thread's x_r slice is dead: it becomes the output
 #pragma unroll
   for (int c = 0; c < CH; ++c) o[c] = hres[c] + (acc[c] * inv + bias[c]);
   SPF_E(10);                                                 // residual + store of the slice
@@ -318,9 +276,8 @@ __global__ __launch_bounds__(THREADS, 2) void spatial_fwd_kernel(const TecmSpati
     bias[c] = d.bias[hh * CH + c];
   }
 
-  const uint32_t dth = d.alpha_drop.p > 0.f ? tecm_drop_thresh(d.alpha_drop.p) : 0u;
-  const float dinv = d.alpha_drop.p > 0.f ? 1.0f / (1.0f - d.alpha_drop.p) : 1.0f;
-  const uint64_t dseed_now = tecm_seed_now(d.alpha_drop.seed, d.alpha_drop.seed_dev);
+  const AlphaDrop dr = alpha_drop_of(d);
+  const uint64_t dseed_now = alpha_drop_seed(d);
   const bool even_cin = (Cin & 1) == 0;
   const unsigned cin_magic = (unsigned)((0x100000000ull + Cin - 1) / Cin);   // idx / Cin == umulhi(idx, magic) for idx * Cin < 2^32
 
@@ -476,12 +433,10 @@ __global__ __launch_bounds__(THREADS, 2) void spatial_fwd_kernel(const TecmSpati
         const float* temb = smem + tb_off + qi * 32;
         if (hh == 0)
           edge_phase<0>(xg, Cin, smem, xl_off, xr_off, hT_off, P, eptr, ecol, temb, tn, i - lo, it.use_edges,
-                        dseed_now, (uint64_t)((rowi * H + 0) * d.alpha_drop.ld), att4, bias, residual,
-                        tf_uniform, dth, dinv);
+                        dseed_now, alpha_drop_base(d, rowi, 0), att4, bias, residual, tf_uniform, dr);
         else
           edge_phase<1>(xg, Cin, smem, xl_off, xr_off, hT_off, P, eptr, ecol, temb, tn, i - lo, it.use_edges,
-                        dseed_now, (uint64_t)((rowi * H + 1) * d.alpha_drop.ld), att4, bias, residual,
-                        tf_uniform, dth, dinv);
+                        dseed_now, alpha_drop_base(d, rowi, 1), att4, bias, residual, tf_uniform, dr);
       }
     }
     SPF_T(7);                                                // own edge work

@@ -21,8 +21,8 @@
 //     neighbour window and the x_r rows of the tile, later its output) -> four blocks = 16 waves per CU, and the
 //     hardware overlaps one block's edge phase with another's transforms and stores;
 //   * the CSR slice is read where it lies (L2-resident: consecutive blocks share the tile).
-// Edge phase, softmax in base 2, |.|-form of LeakyReLU, dropout of the attention coefficients keyed by the logical
-// (row, head, slot) index and the 16-byte output stores are the first kernel's, expression for expression.
+// The edge phase is built from the pieces both forward kernels share (spatial_edge.h): row loads, the |.|-form logit in
+// base 2, the online-softmax step over EU slots, the dropout mask keyed by the logical (row, head, slot) index.
 //
 // Everything the first kernel alone serves (per-node time features, the stand-alone module forwards, odd Cin, output
 // pitches other than 24) stays there: tecm_spatial_fwd2_ws_floats() returns 0 and the caller uses tecm_spatial_fwd.
@@ -33,19 +33,14 @@ using namespace tecm_spatial2;
 
 namespace {
 
-// One thread per (target node, head HH): the first kernel's edge phase reading the CSR from global memory.
+// One thread per (target node, head HH): the edge phase of spatial_fwd.hip, reading the CSR from global memory.
 template <int HH, int CIN>
 __device__ __forceinline__ void edge_phase2(const TecmSpatial& d, const float* __restrict__ xg, const float* __restrict__ emb_row,
                                             const float* __restrict__ temb, const float* xl, float* xr_row, int e0, int deg,
-                                            int lo, int wi, uint64_t dbase, const float (&att4)[CH], const float (&bias)[CH],
-                                            uint32_t dth, float dinv) {
+                                            int lo, int wi, const AlphaDrop& dr, uint64_t dbase, const float (&att4)[CH],
+                                            const float (&bias)[CH]) {
   float xr[CH + 1];                                          // xr[11] = u_r
-  {
-    const float4* p = reinterpret_cast<const float4*>(xr_row + HH * 12);
-    const float4 a = p[0], b = p[1], c = p[2];
-    xr[0] = a.x; xr[1] = a.y; xr[2] = a.z; xr[3] = a.w; xr[4] = b.x; xr[5] = b.y; xr[6] = b.z; xr[7] = b.w;
-    xr[8] = c.x; xr[9] = c.y; xr[10] = c.z; xr[11] = c.w;
-  }
+  ld12(xr_row + HH * HP, xr);
   float hres[CH];                                            // residual input h[i]: issued now, consumed at the very end
 #pragma unroll
   for (int c = 0; c < CH; ++c) {
@@ -53,8 +48,8 @@ __device__ __forceinline__ void edge_phase2(const TecmSpatial& d, const float* _
     hres[c] = ch < CIN ? xg[ch] : emb_row[ch - CIN] + temb[ch - CIN];
   }
   const int* __restrict__ col = d.colidx + e0;
-  const uint64_t dseed = tecm_seed_now(d.alpha_drop.seed, d.alpha_drop.seed_dev);
-  const float base = (0.6f * LOG2E) * xr[11];
+  const uint64_t dseed = alpha_drop_seed(d);
+  const float base = (0.6f * LOG2E) * xr[CH];
   float m = -INFINITY, z = 0.f;
   float acc[CH + 1];
 #pragma unroll
@@ -65,45 +60,13 @@ __device__ __forceinline__ void edge_phase2(const TecmSpatial& d, const float* _
     for (int u = 0; u < EU; ++u) {
       const int sl = s + u;
       const int j = sl < deg ? col[sl] - lo : wi;            // slots past the self loop re-read it and get weight 0
-      const float4* p = reinterpret_cast<const float4*>(xl + j * CP + HH * 12);
-      const float4 q0 = p[0], q1 = p[1], q2 = p[2];
-      a[u][0] = q0.x; a[u][1] = q0.y; a[u][2] = q0.z; a[u][3] = q0.w; a[u][4] = q1.x; a[u][5] = q1.y;
-      a[u][6] = q1.z; a[u][7] = q1.w; a[u][8] = q2.x; a[u][9] = q2.y; a[u][10] = q2.z; a[u][11] = q2.w;
-      float e = fmaf(0.6f * LOG2E, q2.w, base);
-#pragma unroll
-      for (int c = 0; c + 1 < CH; c += 2) {                  // s = x_l[j] + x_r[i] two channels at a time (v_pk_add_f32)
-        const f32x2 sv = f32x2{a[u][c], a[u][c + 1]} + f32x2{xr[c], xr[c + 1]};
-        e = fmaf(att4[c], fabsf(sv.x), e);
-        e = fmaf(att4[c + 1], fabsf(sv.y), e);
-      }
-      e = fmaf(att4[CH - 1], fabsf(a[u][CH - 1] + xr[CH - 1]), e);
-      ev[u] = sl <= deg ? e : -INFINITY;
+      ld12(xl + j * CP + HH * HP, a[u]);
+      ev[u] = sl <= deg ? logit_abs(a[u], xr, att4, base) : -INFINITY;
     }
-    float mn = m;                                            // slot s is always valid: mn is finite
-#pragma unroll
-    for (int u = 0; u < EU; ++u) mn = fmaxf(mn, ev[u]);
-    const float corr = __builtin_amdgcn_exp2f(m - mn);       // exp2(-inf) = 0 on the first step
-    float pm[EU], zs = 0.f;
-#pragma unroll
-    for (int u = 0; u < EU; ++u) {
-      const float p = __builtin_amdgcn_exp2f(ev[u] - mn);
-      zs += p;
-      pm[u] = p;
-      if (dth) pm[u] = p * tecm_drop_mult(dseed, dbase + s + u, dth, dinv);
-    }
-    z = z * corr + zs;
-    m = mn;
-#pragma unroll
-    for (int c = 0; c < CH + 1; c += 2) {                    // channel pairs (the 12th lane of the pair is the unused u)
-      f32x2 t = f32x2{acc[c], acc[c + 1]} * corr;
-#pragma unroll
-      for (int u = 0; u < EU; ++u) t = f32x2{a[u][c], a[u][c + 1]} * pm[u] + t;
-      acc[c] = t.x;
-      acc[c + 1] = t.y;
-    }
+    softmax_step<EU>(a, ev, dr, dseed, dbase + s, m, z, acc);
   }
   const float inv = 1.0f / (z + 1e-16f);
-  float* o = xr_row + HH * 12;                               // this thread's x_r slice is dead: it becomes the output
+  float* o = xr_row + HH * HP;                               // this thread's x_r slice is dead: it becomes the output
 #pragma unroll
   for (int c = 0; c < CH; ++c) o[c] = hres[c] + (acc[c] * inv + bias[c]);
 }
@@ -116,8 +79,8 @@ __global__ __launch_bounds__(T2, 4) void spatial_fwd2_kernel(const TecmSpatial d
   const int N = d.N, G = d.B * d.L;
   const int item = blockIdx.x;
   const int tile = item / G, gm = item - tile * G;           // tile-major: consecutive blocks share the tile's CSR and P rows
-  const int b = gm / d.L, t = gm - b * d.L;
-  const bool use_edges = (t * d.B + b) < d.graphs_with_edges; // the reference's flattening is (L*B): g = t*B + b
+  const Graph gq = decode_graph(d, gm);
+  const bool use_edges = gq.use_edges;
   const int n0 = tile * d.tile_nodes, n1 = min(N, n0 + d.tile_nodes);
   const int lo = d.tile_lo[tile], hi = d.tile_hi[tile];
   const int wa = use_edges ? 0 : n0 - lo, wb = use_edges ? hi - lo : n1 - lo;   // window rows this graph reads
@@ -148,8 +111,7 @@ __global__ __launch_bounds__(T2, 4) void spatial_fwd2_kernel(const TecmSpatial d
     const int tn = tid & (TN2 - 1), hh = tid >> 7;
     const int i = n0 + tn;
     if (i < n1) {
-      const uint32_t dth = d.alpha_drop.p > 0.f ? tecm_drop_thresh(d.alpha_drop.p) : 0u;
-      const float dinv = d.alpha_drop.p > 0.f ? 1.0f / (1.0f - d.alpha_drop.p) : 1.0f;
+      const AlphaDrop dr = alpha_drop_of(d);
       float att4[CH], bias[CH];
 #pragma unroll
       for (int c = 0; c < CH; ++c) {
@@ -158,15 +120,15 @@ __global__ __launch_bounds__(T2, 4) void spatial_fwd2_kernel(const TecmSpatial d
       }
       const int e0 = d.rowptr[i];
       const int deg = use_edges ? d.rowptr[i + 1] - e0 : 0;
-      const int64_t rowi = (int64_t)(t * d.B + b) * N + i;   // row in the reference's (L*B*N) flattening
+      const int64_t rowi = (int64_t)(gq.t * d.B + gq.b) * N + i;   // row in the reference's (L*B*N) flattening
       const float* xg = d.x + (grow + i) * CIN;
       const float* emb_row = d.node_tab + (int64_t)i * d.Demb;
       if (hh == 0)
-        edge_phase2<0, CIN>(d, xg, emb_row, gv + 48, xl, xr + tn * CP, e0, deg, lo, i - lo,
-                            (uint64_t)((rowi * H + 0) * d.alpha_drop.ld), att4, bias, dth, dinv);
+        edge_phase2<0, CIN>(d, xg, emb_row, gv + 48, xl, xr + tn * CP, e0, deg, lo, i - lo, dr,
+                            alpha_drop_base(d, rowi, 0), att4, bias);
       else
-        edge_phase2<1, CIN>(d, xg, emb_row, gv + 48, xl, xr + tn * CP, e0, deg, lo, i - lo,
-                            (uint64_t)((rowi * H + 1) * d.alpha_drop.ld), att4, bias, dth, dinv);
+        edge_phase2<1, CIN>(d, xg, emb_row, gv + 48, xl, xr + tn * CP, e0, deg, lo, i - lo, dr,
+                            alpha_drop_base(d, rowi, 1), att4, bias);
     }
   }
   __syncthreads();

@@ -120,6 +120,29 @@ def _empty(*shape, like: torch.Tensor) -> torch.Tensor:
 
 
 # ============================================================================ stage a-1..a-3
+def _spatial_param_grads(d: TecmSpatial, g: TecmSpatialGrads, dout, meta: GraphMeta, att, v2: bool):
+    """The parameter launch of the spatial backward (csrc/spatial_bwd2.hip where `v2` allows it and it serves the call, else
+    csrc/spatial_bwd.hip) and its partial-sum rows [dWl (C*C) | dbl (C) | dWr (C*C) | dbr (C) | datt (C) | unused (C)], one
+    per block, summed and taken apart: (dWl, dbl, dWr, dbr, datt).  `g` arrives with the table gradients set, or none."""
+    Cc = C_FEAT
+    pld = 2 * Cc * Cc + 4 * Cc
+    nb2 = lib().tecm_spatial_bwd2_blocks(C.byref(d)) if v2 else 0
+    nblocks = nb2 if nb2 > 0 else lib().tecm_spatial_bwd_blocks(C.byref(d))   # rows of the partial-sum buffer
+    if nblocks <= 0:
+        check(nblocks, "tecm_spatial_bwd_blocks")
+    partials = _empty(nblocks, pld, like=dout)
+    g.dout, g.partials, g.partial_ld, g.num_blocks = dout.data_ptr(), partials.data_ptr(), pld, nblocks
+    g.src_ptr, g.src_col, g.src_ptr_off = meta.src_ptr.data_ptr(), meta.src_col.data_ptr(), meta.src_ptr_off.data_ptr()
+    if nb2 > 0:
+        ws = torch.empty(lib().tecm_spatial_fwd2_ws_floats(C.byref(d)), device=dout.device, dtype=torch.float32)
+        check(lib().tecm_spatial_bwd2(C.byref(d), C.byref(g), ws.data_ptr(), stream_ptr()), "tecm_spatial_bwd2")
+    else:
+        check(lib().tecm_spatial_bwd(C.byref(d), C.byref(g), stream_ptr()), "tecm_spatial_bwd")
+    s = colsum(partials, pld, nblocks, 1, 1, pld)[0]
+    dWl, dbl, dWr, dbr, datt, _ = s.split([Cc * Cc, Cc, Cc * Cc, Cc, Cc, Cc])
+    return dWl.view(Cc, Cc), dbl, dWr.view(Cc, Cc), dbr, datt.view_as(att)
+
+
 class SpatialFn(torch.autograd.Function):
     """SpatioTemporalEmbedding + GATv2Conv + residual (modules.py:230-266, :340-359; tec_mollm.py:84-94)."""
 
@@ -190,13 +213,6 @@ class SpatialFn(torch.autograd.Function):
         # round 5: the second formulation (csrc/spatial_bwd2.hip) wherever it serves the call; TECM_SPATIAL_V2=0 / TECM_SPATIAL_BWD2=0
         # keep the persistent kernel (A/B)
         v2 = os.environ.get("TECM_SPATIAL_V2", "1")[:1] != "0" and os.environ.get("TECM_SPATIAL_BWD2", "1")[:1] != "0"
-        nb2 = lib().tecm_spatial_bwd2_blocks(C.byref(d)) if v2 else 0
-        nblocks = nb2 if nb2 > 0 else lib().tecm_spatial_bwd_blocks(C.byref(d))   # rows of the partial-sum buffer
-        if nblocks <= 0:
-            check(nblocks, "tecm_spatial_bwd_blocks")
-        Cc = C_FEAT
-        pld = 2 * Cc * Cc + 4 * Cc
-        partials = _empty(nblocks, pld, like=x)
         tabs = (node_tab, tod_tab, doy_tab, year_tab, season_tab)          # the kernel accumulates into them: ONE zero fill
         zbuf = torch.zeros(sum(t.numel() for t in tabs), device=x.device, dtype=torch.float32)
         offs = [0]
@@ -204,26 +220,10 @@ class SpatialFn(torch.autograd.Function):
             offs.append(offs[-1] + t.numel())
         d_node, d_tod, d_doy, d_year, d_season = (zbuf[a:b].view_as(t) for t, a, b in zip(tabs, offs[:-1], offs[1:]))
         g = TecmSpatialGrads()
-        g.dout = dout.data_ptr()
         g.d_node_tab, g.d_tod_tab, g.d_doy_tab = d_node.data_ptr(), d_tod.data_ptr(), d_doy.data_ptr()
         g.d_year_tab, g.d_season_tab = d_year.data_ptr(), d_season.data_ptr()
-        g.partials, g.partial_ld = partials.data_ptr(), pld
-        g.t_chunk, g.num_blocks = 0, nblocks
-        g.src_ptr, g.src_col = meta.src_ptr.data_ptr(), meta.src_col.data_ptr()
-        g.src_ptr_off = meta.src_ptr_off.data_ptr()
-        if nb2 > 0:
-            ws = torch.empty(lib().tecm_spatial_fwd2_ws_floats(C.byref(d)), device=x.device, dtype=torch.float32)
-            check(lib().tecm_spatial_bwd2(C.byref(d), C.byref(g), ws.data_ptr(), stream_ptr()), "tecm_spatial_bwd2")
-        else:
-            check(lib().tecm_spatial_bwd(C.byref(d), C.byref(g), stream_ptr()), "tecm_spatial_bwd")
-        s = colsum(partials, pld, nblocks, 1, 1, pld)[0]
-        o = 0
-        dWl = s[o:o + Cc * Cc].view(Cc, Cc); o += Cc * Cc
-        dbl = s[o:o + Cc]; o += Cc
-        dWr = s[o:o + Cc * Cc].view(Cc, Cc); o += Cc * Cc
-        dbr = s[o:o + Cc]; o += Cc
-        datt = s[o:o + Cc].view_as(att)
-        dbias = colsum(dout, CP, B * L * N, 1, 1, CP)[0, :Cc]   # d bias = column sums of dout (out = h + gat + bias);
+        dWl, dbl, dWr, dbr, datt = _spatial_param_grads(d, g, dout, meta, att, v2)
+        dbias = colsum(dout, CP, B * L * N, 1, 1, CP)[0, :C_FEAT]   # d bias = column sums of dout (out = h + gat + bias);
         #                                                         all 24 padded columns: the float4 reduction path
         return (dx, None, d_node, d_tod, d_doy, d_year, d_season, dWl, dbl, dWr, dbr, datt, dbias,
                 None, None, None, None)
@@ -337,23 +337,7 @@ class GatFn(torch.autograd.Function):
         dpad = torch.zeros(G, 1, N, CP, device=x.device, dtype=torch.float32)
         dpad[..., :Cc] = dout.reshape(G, 1, N, Cc)
         d = GatFn._desc(x, Wl, bl, Wr, br, att, bias, ctx.meta, ctx.heads, ctx.R, ctx.plan)
-        nblocks = lib().tecm_spatial_bwd_blocks(C.byref(d))
-        if nblocks <= 0:
-            check(nblocks, "tecm_spatial_bwd_blocks")
-        pld = 2 * Cc * Cc + 4 * Cc
-        partials = _empty(nblocks, pld, like=x)
-        g = TecmSpatialGrads()
-        g.dout, g.partials, g.partial_ld, g.num_blocks = dpad.data_ptr(), partials.data_ptr(), pld, nblocks
-        meta = ctx.meta
-        g.src_ptr, g.src_col, g.src_ptr_off = meta.src_ptr.data_ptr(), meta.src_col.data_ptr(), meta.src_ptr_off.data_ptr()
-        check(lib().tecm_spatial_bwd(C.byref(d), C.byref(g), stream_ptr()), "tecm_spatial_bwd(GAT only)")
-        s = colsum(partials, pld, nblocks, 1, 1, pld)[0]
-        o = 0
-        dWl = s[o:o + Cc * Cc].view(Cc, Cc); o += Cc * Cc
-        dbl = s[o:o + Cc]; o += Cc
-        dWr = s[o:o + Cc * Cc].view(Cc, Cc); o += Cc * Cc
-        dbr = s[o:o + Cc]; o += Cc
-        datt = s[o:o + Cc].view_as(att)
+        dWl, dbl, dWr, dbr, datt = _spatial_param_grads(d, TecmSpatialGrads(), dpad, ctx.meta, att, v2=False)
         dbias = colsum(dpad, CP, G * N, 1, 1, CP)[0, :Cc]
         return (None, dWl, dbl, dWr, dbr, datt, dbias, None, None, None, None)
 

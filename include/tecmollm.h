@@ -88,8 +88,14 @@ enum { TECM_ACT_NONE = 0, TECM_ACT_GELU_ERF = 1, TECM_ACT_GELU_TANH = 2 };
  *   outside [0, Lin) is dropped).  split_k > 1 applies the same epilogue to the reduced sum.
  * tests/gemm_epilogue_ref.py states this order in fp64; tests/test_gpu_gemm_epilogue.py holds every kernel family to it. */
 /* io_bf16 (tecm_gemm_bf16 only, 0 everywhere else): which tensors of the call already are / shall be bf16 in HBM.
- * A bf16 operand is [row][k] with k contiguous and its leading dimension counted in bf16 elements (multiple of 8,
- * 16-byte aligned, K % 8 == 0); the call must be the plain MK x NK contraction.  TECM_IO_C_BF16 writes C as bf16
+ * A bf16 operand has its leading dimension counted in bf16 elements (multiple of 8, 16-byte aligned base) and a contiguous
+ * extent that is a multiple of 8: K for [row][k] storage, M for A stored [k][m], N for B stored [k][n]; a window view of it
+ * needs Cw % 8 == 0 (TECM_E_ALIGN / TECM_E_ARG otherwise).  Served: MK x NK with plain views -- A, B or both; MK x NK behind
+ * a window -- A alone behind a_win (both only where the LDS-DMA kernels take the view: pad-free taps of whole K-tiles);
+ * MK x KN -- A alone; KM x KN -- A, B or both.  An fp32 partner needs the float4 loader (16-byte aligned, leading dimension,
+ * and K where k is contiguous, multiples of 4); every other combination is TECM_E_ARG.  tests/test_gpu_gemm_shapes.py
+ * holds each of these to the contract either side of its tile edges and asserts the refusals.
+ * TECM_IO_C_BF16 writes C as bf16
  * (ldc in bf16 elements; needs the float4-friendly epilogue, no residual / accumulate / c_win / split_k); preact,
  * dact_src, bias stay fp32.  Rounding an activation once where it is produced instead of at every consumer's
  * loader gives bit-identical results at half the bytes.

@@ -150,6 +150,13 @@ int32_t tecm_gemm_tn_splits(int64_t M, int64_t N, int64_t K);
  * M x N result on this device: the height whose tile count wastes least of the last round of CUs (csrc/gemm_bf16_p8.hip).
  * Exposed so that a caller's per-kernel accounting can name the instantiation a call runs on. */
 int tecm_p8_rows(int64_t M, int64_t N);
+/* The block -> tile map the bf16 and split-bf16 GEMM kernels apply to blockIdx.x (csrc/gemm_tile_map.h, compiled here for
+ * the host; the fp32 kernel carries the same formula inline): block `id` of a tiles_m x tiles_n grid whose L2 super-tiles
+ * are group_m m-tiles tall computes tile (*tm, *tn).  Exposed so that a host test can check the map is a bijection.  Pure
+ * host function. */
+void tecm_gemm_tile_of_block(int id, int tiles_m, int tiles_n, int group_m, int* tm, int* tn);
+/* The same for every id in 0 .. tiles_m * tiles_n - 1 in one call: tm[id], tn[id]. */
+void tecm_gemm_tiles_of_blocks(int tiles_m, int tiles_n, int group_m, int* tm, int* tn);
 /* Name of the contraction kernel (template arguments included, e.g. "gemm_kernel<0,0,4,4,128,false,false,128>") that this
  * thread's most recent successful tecm_gemm_* call launched; the split-K reducer and the erf-GELU pass behind it are not
  * reported.  "" before the first call, unspecified after a failed one.  Host pointer, valid for the life of the library.

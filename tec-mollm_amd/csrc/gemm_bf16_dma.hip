@@ -53,21 +53,10 @@ __global__ __launch_bounds__(DNTH, 1) void gemm_bf16_dma_kernel(const TecmGemm g
   __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
   static_assert(2 * TILE_ELEMS * 2 >= 8 * 32 * (WTN + 4) * 4, "epilogue slabs fit in the operand buffers");
 
-  // block -> tile map: XCD-contiguous runs, GROUP_M m-tiles per L2 super-tile (as gemm_bf16_kernel)
-  const int nwg = tiles_m * tiles_n;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  const int GROUP_M = g._p1 > 0 ? g._p1 : 4;              // m-tiles per L2 super-tile (ops.GROUP_M sweeps it)
-  const int per_group = GROUP_M * tiles_n;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * per_group;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * DBM;
-  const int64_t n0 = (int64_t)tn * DBN;
+  // block -> tile (gemm_tile_map.h); m-tiles per L2 super-tile: 4, or what ops.GROUP_M sweeps
+  const tecm_gemm::TileIdx blk = tecm_gemm::tile_of_block(blockIdx.x, tiles_m, tiles_n, g._p1 > 0 ? g._p1 : 4);
+  const int64_t m0 = (int64_t)blk.tm * DBM;
+  const int64_t n0 = (int64_t)blk.tn * DBN;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -201,14 +190,7 @@ __global__ __launch_bounds__(DNTH, 1) void gemm_bf16_dma_kernel(const TecmGemm g
   }
 
 #ifdef DMA_ABLATE_NOEPI                                  // diagnostics (tools/build_variant.py): K loop without the epilogue
-  float keep = 0.f;
-#pragma unroll
-  for (int i = 0; i < MT; ++i)
-#pragma unroll
-    for (int j = 0; j < NT; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) keep += acc[i][j][e];
-  if (keep == 12345.678f) reinterpret_cast<float*>(g.C)[0] = keep;
+  ablate_noepi_sink(g, acc);
 #else
   // non-temporal stores: C and the pre-activation stream past L2 instead of evicting the operand panels the next
   // tiles of this XCD are about to read (N=3072 K=768: 512 -> 476 us, N=2304 K=800: 409 -> 367; no effect on the fp32
@@ -247,20 +229,10 @@ __global__ __launch_bounds__(D2TH, 4) void gemm_bf16_dma2_kernel(const TecmGemm 
   __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
   static_assert(D2ST * TILE_ELEMS * 2 >= 8 * 32 * (WTN + 4) * 4, "epilogue slabs fit in the operand ring");
 
-  const int nwg = tiles_m * tiles_n;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  const int GROUP_M = g._p1 > 0 ? g._p1 : 4;
-  const int per_group = GROUP_M * tiles_n;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * per_group;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * D2M;
-  const int64_t n0 = (int64_t)tn * D2N;
+  // block -> tile (gemm_tile_map.h); m-tiles per L2 super-tile: 4, or what ops.GROUP_M sweeps
+  const tecm_gemm::TileIdx blk = tecm_gemm::tile_of_block(blockIdx.x, tiles_m, tiles_n, g._p1 > 0 ? g._p1 : 4);
+  const int64_t m0 = (int64_t)blk.tm * D2M;
+  const int64_t n0 = (int64_t)blk.tn * D2N;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -378,20 +350,10 @@ __global__ __launch_bounds__(D3TH, 1) void gemm_bf16_dma3_kernel(const TecmGemm 
   __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
   static_assert(D3ST * TILE_ELEMS * 2 >= 8 * 32 * (WTN + 4) * 4, "epilogue slabs fit in the operand ring");
 
-  const int nwg = tiles_m * tiles_n;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  const int GROUP_M = g._p1 > 0 ? g._p1 : 4;
-  const int per_group = GROUP_M * tiles_n;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * per_group;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * D3M;
-  const int64_t n0 = (int64_t)tn * D3N;
+  // block -> tile (gemm_tile_map.h); m-tiles per L2 super-tile: 4, or what ops.GROUP_M sweeps
+  const tecm_gemm::TileIdx blk = tecm_gemm::tile_of_block(blockIdx.x, tiles_m, tiles_n, g._p1 > 0 ? g._p1 : 4);
+  const int64_t m0 = (int64_t)blk.tm * D3M;
+  const int64_t n0 = (int64_t)blk.tn * D3N;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -519,20 +481,10 @@ __global__ __launch_bounds__(D3TH, 1) void gemm_bf16_dma4_kernel(const TecmGemm 
   __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
   static_assert(D3ST * TILE_ELEMS * 2 >= 8 * 32 * (WTN + 4) * 4, "epilogue slabs fit in the operand ring");
 
-  const int nwg = tiles_m * tiles_n;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  const int GROUP_M = g._p1 > 0 ? g._p1 : 4;
-  const int per_group = GROUP_M * tiles_n;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * per_group;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * D3M;
-  const int64_t n0 = (int64_t)tn * D3N;
+  // block -> tile (gemm_tile_map.h); m-tiles per L2 super-tile: 4, or what ops.GROUP_M sweeps
+  const tecm_gemm::TileIdx blk = tecm_gemm::tile_of_block(blockIdx.x, tiles_m, tiles_n, g._p1 > 0 ? g._p1 : 4);
+  const int64_t m0 = (int64_t)blk.tm * D3M;
+  const int64_t n0 = (int64_t)blk.tn * D3N;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -702,6 +654,23 @@ __global__ __launch_bounds__(D3TH, 1) void gemm_bf16_dma4_kernel(const TecmGemm 
 // The summation order inside an MFMA differs from the 32x32x16 kernels': results agree to fp32 rounding, not bit for bit.
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
+// Parks TILES 16-row tiles of a wave's accumulators, from row tile I0 on, in its private staging rows (2: a 32-row slab,
+// 1: a half slab).  C/D map of the 16x16 MFMA: row = 4 fq + reg, col = fr, with fr = lane & 15, fq = lane >> 4.
+template <int I0, int TILES, int MT, int NT>
+__device__ __forceinline__ void park_tiles16(float* stg, const f32x4v (&acc)[MT][NT], int fq, int fr) {
+  constexpr int STG_LD = NT * 16 + 4;
+  static_for<TILES>([&](auto tc) {
+    constexpr int ti = decltype(tc)::value;
+    static_for<NT>([&](auto jc) {
+      constexpr int jn = decltype(jc)::value;
+      static_for<4>([&](auto ec) {
+        constexpr int e = decltype(ec)::value;
+        stg[(16 * ti + 4 * fq + e) * STG_LD + jn * 16 + fr] = acc[I0 + ti][jn][e];
+      });
+    });
+  });
+}
+
 // (Round 4: the body is a template on the tile height BM.  BM = 288 -- nine 16-row MFMA tiles per wave instead of eight --
 //  exists for ONE reason: M = 69 864 rows are 273 m-tiles of 256, and with N = 768 (three n-tiles) that is 819 tiles = 3.2
 //  rounds of 256 CUs: the fourth round runs 51 tiles on 256 CUs and costs a full tile time (measured: M = 65 536 332 us,
@@ -720,20 +689,10 @@ __device__ __forceinline__ void gemm_bf16_dma5_body(const TecmGemm& g, int tiles
   __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
   static_assert(D3ST * TILE_ELEMS * 2 >= 8 * 32 * (WTN + 4) * 4, "epilogue slabs fit in the operand ring");
 
-  const int nwg = tiles_m * tiles_n;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  const int GROUP_M = g._p1 > 0 ? g._p1 : 4;
-  const int per_group = GROUP_M * tiles_n;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * per_group;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * BM;
-  const int64_t n0 = (int64_t)tn * D3N;
+  // block -> tile (gemm_tile_map.h); m-tiles per L2 super-tile: 4, or what ops.GROUP_M sweeps
+  const tecm_gemm::TileIdx blk = tecm_gemm::tile_of_block(blockIdx.x, tiles_m, tiles_n, g._p1 > 0 ? g._p1 : 4);
+  const int64_t m0 = (int64_t)blk.tm * BM;
+  const int64_t n0 = (int64_t)blk.tn * D3N;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -848,55 +807,30 @@ __device__ __forceinline__ void gemm_bf16_dma5_body(const TecmGemm& g, int tiles
   }
   __syncthreads();                                      // every wave has left the last K-tile: the ring becomes staging
 #ifdef DMA_ABLATE_NOEPI                                  // diagnostics (tools/build_variant.py): K loop without the epilogue
-  {
-    float keep = 0.f;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) keep += acc[i][j][e];
-    if (keep == 12345.678f) reinterpret_cast<float*>(g.C)[0] = keep;
-    return;
-  }
+  ablate_noepi_sink(g, acc);
+  return;
 #endif
 
-  // ---- epilogue: gemm_impl.h's straight-line form over this wave's private staging rows; only the parking of the
-  // accumulators knows the 16x16 C/D map (row = 4 (lane >> 4) + reg, col = lane & 15)
+  // ---- epilogue: gemm_impl.h's straight-line form over this wave's private staging rows (the mode is >= 0: checked on
+  // the host, tecm_gemm16_dma_try); only the parking of the accumulators knows the 16x16 C/D map (park_tiles16)
   constexpr int STG_LD = WTN + 4;
   const DropCtx odc = make_drop(g.out_drop);
   float* stg = reinterpret_cast<float*>(smem_raw) + wave * (32 * STG_LD);
-  auto stage_slab = [&](auto ic) {                     // 32 accumulator rows = tile rows 2 i, 2 i + 1
-    constexpr int i = decltype(ic)::value;
-    static_for<2>([&](auto tc) {
-      constexpr int ti = decltype(tc)::value;
-      static_for<NT>([&](auto jc) {
-        constexpr int jn = decltype(jc)::value;
-        static_for<4>([&](auto ec) {
-          constexpr int e = decltype(ec)::value;
-          stg[(16 * ti + 4 * fq + e) * STG_LD + jn * 16 + fr] = acc[2 * i + ti][jn][e];
-        });
-      });
-    });
-  };
-  const int fmode = tecm_gemm::epi_fast_mode(g);         // >= 0: checked on the host (tecm_gemm16_dma_try)
-  constexpr int LPR = WTN / 4, RPI = 64 / LPR;
-  const int lcol = (lane % LPR) * 4, lrow = lane / LPR;
-  const EpiCol ecol = epi_col(g, n0 + wn * WTN + lcol);
-  float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (g.bias) bias4 = *reinterpret_cast<const float4*>(g.bias + (ecol.ok ? ecol.n : 0));   // (lanes outside the matrix: column 0, never stored)
-  tecm_gemm::epi_fast_dispatch<MT / 2, 32 / RPI, RPI, STG_LD, true>(fmode, g, odc, stg, lrow, lcol, m0 + wm * WTM, ecol, bias4,
-                                                                stage_slab);
-  if constexpr (MT % 2 == 1) {                           // the ninth row tile: a half slab of 16 rows
-    auto stage_last = [&](auto) {
-      static_for<NT>([&](auto jc) {
-        constexpr int jn = decltype(jc)::value;
-        static_for<4>([&](auto ec) {
-          constexpr int e = decltype(ec)::value;
-          stg[(4 * fq + e) * STG_LD + jn * 16 + fr] = acc[MT - 1][jn][e];
-        });
-      });
-    };
+  auto stage_slab = [&](auto ic) { park_tiles16<2 * decltype(ic)::value, 2>(stg, acc, fq, fr); };
+  if constexpr (MT % 2 == 0) {
+    tecm_gemm::epi_fast_tail<MT / 2, 32, WTN, true>(g, g, odc, stg, lane, m0 + wm * WTM, n0 + wn * WTN, stage_slab);
+  } else {
+    // nine row tiles: four slabs and a half slab of 16 rows behind ONE lane set-up (epi_fast_tail's, written out: calling
+    // the tail twice changes this kernel's register allocation -- profiles/gemm_shared_frame_resources.md)
+    const int fmode = tecm_gemm::epi_fast_mode(g);
+    constexpr int LPR = WTN / 4, RPI = 64 / LPR;
+    const int lcol = (lane % LPR) * 4, lrow = lane / LPR;
+    const EpiCol ecol = epi_col(g, n0 + wn * WTN + lcol);
+    float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g.bias) bias4 = *reinterpret_cast<const float4*>(g.bias + (ecol.ok ? ecol.n : 0));   // (lanes outside the matrix: column 0, never stored)
+    tecm_gemm::epi_fast_dispatch<MT / 2, 32 / RPI, RPI, STG_LD, true>(fmode, g, odc, stg, lrow, lcol, m0 + wm * WTM, ecol, bias4,
+                                                                  stage_slab);
+    auto stage_last = [&](auto) { park_tiles16<MT - 1, 1>(stg, acc, fq, fr); };
     tecm_gemm::epi_fast_dispatch<1, 16 / RPI, RPI, STG_LD, true>(fmode, g, odc, stg, lrow, lcol, m0 + wm * WTM + (MT - 1) * 16, ecol,
                                                               bias4, stage_last);
   }
@@ -938,20 +872,10 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_dma6_kernel(const TecmGemm g
   __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
   static_assert(ST * TILE_ELEMS * 2 >= 4 * 32 * (WTN + 4) * 4, "epilogue slabs fit in the operand ring");
 
-  const int nwg = tiles_m * tiles_n;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  const int GROUP_M = g._p1 > 0 ? g._p1 : 4;
-  const int per_group = GROUP_M * tiles_n;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * per_group;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * BM;
-  const int64_t n0 = (int64_t)tn * BN;
+  // block -> tile (gemm_tile_map.h); m-tiles per L2 super-tile: 4, or what ops.GROUP_M sweeps
+  const tecm_gemm::TileIdx blk = tecm_gemm::tile_of_block(blockIdx.x, tiles_m, tiles_n, g._p1 > 0 ? g._p1 : 4);
+  const int64_t m0 = (int64_t)blk.tm * BM;
+  const int64_t n0 = (int64_t)blk.tn * BN;
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wm = wave / WN, wn = wave % WN;
@@ -1060,30 +984,10 @@ __global__ __launch_bounds__(256, 2) void gemm_bf16_dma6_kernel(const TecmGemm g
   }
   __syncthreads();                                      // every wave has left the last K-tile: the ring becomes staging
 
-  constexpr int STG_LD = WTN + 4;
   const DropCtx odc = make_drop(g.out_drop);
-  float* stg = reinterpret_cast<float*>(smem_raw) + wave * (32 * STG_LD);
-  auto stage_slab = [&](auto ic) {                     // 32 accumulator rows = tile rows 2 i, 2 i + 1
-    constexpr int i = decltype(ic)::value;
-    static_for<2>([&](auto tc) {
-      constexpr int ti = decltype(tc)::value;
-      static_for<NT>([&](auto jc) {
-        constexpr int jn = decltype(jc)::value;
-        static_for<4>([&](auto ec) {
-          constexpr int e = decltype(ec)::value;
-          stg[(16 * ti + 4 * fq + e) * STG_LD + jn * 16 + fr] = acc[2 * i + ti][jn][e];
-        });
-      });
-    });
-  };
-  const int fmode = tecm_gemm::epi_fast_mode(g);
-  constexpr int LPR = WTN / 4, RPI = 64 / LPR;
-  const int lcol = (lane % LPR) * 4, lrow = lane / LPR;
-  const EpiCol ecol = epi_col(g, n0 + wn * WTN + lcol);
-  float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (g.bias) bias4 = *reinterpret_cast<const float4*>(g.bias + (ecol.ok ? ecol.n : 0));   // (lanes outside the matrix: column 0, never stored)
-  tecm_gemm::epi_fast_dispatch<WTM / 32, 32 / RPI, RPI, STG_LD, true>(fmode, g, odc, stg, lrow, lcol, m0 + wm * WTM, ecol, bias4,
-                                                                  stage_slab);
+  float* stg = reinterpret_cast<float*>(smem_raw) + wave * (32 * (WTN + 4));
+  auto stage_slab = [&](auto ic) { park_tiles16<2 * decltype(ic)::value, 2>(stg, acc, fq, fr); };
+  tecm_gemm::epi_fast_tail<WTM / 32, 32, WTN, true>(g, g, odc, stg, lane, m0 + wm * WTM, n0 + wn * WTN, stage_slab);
 }
 
 }  // namespace tecm_gemm16
@@ -1101,12 +1005,11 @@ int tecm_gemm16_dma_try(const TecmGemm& g, hipStream_t st) {
   if (!both || !(g.io_bf16 & TECM_P0_VEC4) || g.split_k > 1 || g.K % 32 != 0 || g.K < 32 || g.M < DBM || g.N < 32 ||
       ((k32 || n_small) && g.a_win.enabled) || (n_small && g.N > 32))    // N = 64 (first 1x1 conv): the register-staged
     return 0;                                                               //   kernel's 64-column tile is faster (114 vs 124 us)
-  // the straight-line epilogues (gemm_impl.h: epi_fast_mode >= 0): at most one input stream; or a row bias; or an fp32
-  // window scatter with nothing but bias / activation / dropout
-  const int n_streams = (g.residual ? 1 : 0) + (g.dact_src ? 1 : 0) + (g.accumulate ? 1 : 0);
-  const bool fast_epi = g.c_win.enabled ? (n_streams == 0 && !g.rowbias && !g.preact &&
-                                           !(g.io_bf16 & (TECM_IO_C_BF16 | TECM_IO_PRE_BF16)))
-                                        : (g.rowbias ? n_streams == 0 : n_streams <= 1);
+  // the straight-line epilogues (gemm_impl.h: epi_fast_mode_of >= 0): at most one input stream; or a row bias (5); or an
+  // fp32 window scatter with nothing but bias / activation / dropout (6).  The eight-phase geometry takes all of them, the
+  // 16x16 ring geometries the plain ones (0..3); split_k <= 1 here, so never 4
+  const int fmode = tecm_gemm::epi_fast_mode_of(g, false);
+  const bool fast_epi = fmode >= 0, can16 = fmode >= 0 && fmode <= 3;
   if (g.a_win.enabled) {
     // a pad-free window view of A whose taps are whole K-tiles (the patch projection's 'b (p l) d -> b p (l d)',
     // modules.py:114): the eight-phase geometry (round 5), else the first geometry -- both move their source pointers one
@@ -1116,11 +1019,8 @@ int tecm_gemm16_dma_try(const TecmGemm& g, hipStream_t st) {
     if (g.b_win.enabled || w.pad != 0 || w.Cw % DBK != 0 || (int64_t)(w.Lout - 1) * w.stride_t + w.taps > w.Lin ||
         g.M % ((int64_t)w.Lout * w.N) != 0)
       return 0;
-    const int wtm = (int)((g.M + DBM - 1) / DBM), wtn = (int)((g.N + DBN - 1) / DBN);
-    hipLaunchKernelGGL(gemm_bf16_dma_kernel, dim3((unsigned)(wtm * wtn)), dim3(DNTH), 0, st, g, wtm, wtn);
-    TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma-window");
-    tecm_gemm_kernel = "gemm_bf16_dma_kernel";
-    return 1;
+    return launch_tiles(gemm_bf16_dma_kernel, "gemm_bf16_dma_kernel", "tecm_gemm_bf16/dma-window", (int)((g.M + DBM - 1) / DBM),
+                        (int)((g.N + DBN - 1) / DBN), DNTH, g, st);
   }
   // round 5: the eight-phase geometry (gemm_bf16_p8.hip) wherever it is eligible (it declines n-tiles that are mostly
   // padding, N = 800, unless forced); TECM_BF16_P8 = 0 or any TECM_BF16_DMA selection keeps the older geometries
@@ -1129,13 +1029,9 @@ int tecm_gemm16_dma_try(const TecmGemm& g, hipStream_t st) {
   // TECM_BF16_DMA = 1 / 2 forces one of the two (A/B diagnostics, tools/dma_ab.sh)
   const int nrem = (int)(g.N % DBN);
   const bool narrow = n_small || (sel && !k32 ? sel[0] == '2' : (nrem >= 1 && nrem <= D2N));
-  if (narrow) {
-    const int t2m = (int)((g.M + D2M - 1) / D2M), t2n = (int)((g.N + D2N - 1) / D2N);
-    hipLaunchKernelGGL(gemm_bf16_dma2_kernel, dim3((unsigned)(t2m * t2n)), dim3(D2TH), 0, st, g, t2m, t2n);
-    TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma2");
-    tecm_gemm_kernel = "gemm_bf16_dma2_kernel";
-    return 1;
-  }
+  if (narrow)
+    return launch_tiles(gemm_bf16_dma2_kernel, "gemm_bf16_dma2_kernel", "tecm_gemm_bf16/dma2", (int)((g.M + D2M - 1) / D2M),
+                        (int)((g.N + D2N - 1) / D2N), D2TH, g, st);
   const int tiles_m = (int)((g.M + DBM - 1) / DBM);
   const int tiles_n = (int)((g.N + DBN - 1) / DBN);
   // TECM_BF16_DMA = 3 / 4: the four-slot ring, plain and with anti-phase wave groups (A/B diagnostics, tools/dma_ab.sh).
@@ -1146,61 +1042,31 @@ int tecm_gemm16_dma_try(const TecmGemm& g, hipStream_t st) {
   // 397 -> 348 us (no zero-filled half K-tile), K = 3072 456 -> 412 us plain and a tie with the residual epilogue, N = 3072
   // K = 768 a tie, K = 768 N = 768 0..-5 %; in the step 392.1 samples/s against 389.0 with it on K = 800 / K >= 2048 only and
   // 386.8 without (one box).  TECM_BF16_DMA = 5 forces it (also for N = 800), 1 forbids it.
-  {
-    const int streams = (g.residual ? 1 : 0) + (g.dact_src ? 1 : 0) + (g.accumulate ? 1 : 0);
-    const bool can16 = !g.c_win.enabled && !g.rowbias && streams <= 1;     // the straight-line epilogues only
-    if (can16 && sel && (sel[0] == '6' || sel[0] == '7')) {                // four-wave blocks, two per CU (A/B diagnostics)
-      if (sel[0] == '6') {
-        const int t6m = (int)((g.M + 255) / 256), t6n = (int)((g.N + 127) / 128);
-        hipLaunchKernelGGL((gemm_bf16_dma6_kernel<256, 128, 2, 2>), dim3((unsigned)(t6m * t6n)), dim3(256), 0, st, g, t6m, t6n);
-        tecm_gemm_kernel = "gemm_bf16_dma6_kernel<256,128,2,2>";
-      } else {
-        const int t6m = (int)((g.M + 127) / 128), t6n = (int)((g.N + 255) / 256);
-        hipLaunchKernelGGL((gemm_bf16_dma6_kernel<128, 256, 1, 4>), dim3((unsigned)(t6m * t6n)), dim3(256), 0, st, g, t6m, t6n);
-        tecm_gemm_kernel = "gemm_bf16_dma6_kernel<128,256,1,4>";
-      }
-      TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma6");
-      return 1;
-    }
-    const bool want16 = (sel && !k32) ? (sel[0] == '5' || sel[0] == '8') : true;
-    if (k32 && !can16) return 0;                           // the 64-deep geometries below cannot take K = 32
-    if (can16 && want16) {
-      // tile height: 256 rows, or 288 where that saves a mostly empty last round of blocks on the 256 CUs (N = 768 at
-      // M = 69 864: 819 tiles = 3.2 rounds of 256-row tiles, 729 = 2.85 rounds of 288-row ones); TECM_BF16_DMA = 5 / 8 force one
-      auto cost = [&](int64_t bm) {
-        const int64_t t = ((g.M + bm - 1) / bm) * tiles_n;
-        return ((t + 255) / 256) * bm;
-      };
-      const char* tl = std::getenv("TECM_BF16_TALL");      // "0": never (A/B diagnostics)
-      const bool tall = sel && sel[0] == '8' ? true : ((sel && sel[0] == '5') || (tl && tl[0] == '0') ? false : cost(288) * 100 < cost(DBM) * 95);
-      if (tall) {
-        const int tm288 = (int)((g.M + 287) / 288);
-        hipLaunchKernelGGL(gemm_bf16_dma5w_kernel, dim3((unsigned)(tm288 * tiles_n)), dim3(D3TH), 0, st, g, tm288, tiles_n);
-        TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma5w");
-        tecm_gemm_kernel = "gemm_bf16_dma5w_kernel";
-        return 1;
-      }
-      hipLaunchKernelGGL(gemm_bf16_dma5_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(D3TH), 0, st, g, tiles_m, tiles_n);
-      TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma5");
-      tecm_gemm_kernel = "gemm_bf16_dma5_kernel";
-      return 1;
-    }
+  if (can16 && sel && sel[0] == '6')                         // four-wave blocks, two per CU (A/B diagnostics)
+    return launch_tiles(gemm_bf16_dma6_kernel<256, 128, 2, 2>, "gemm_bf16_dma6_kernel<256,128,2,2>", "tecm_gemm_bf16/dma6",
+                        (int)((g.M + 255) / 256), (int)((g.N + 127) / 128), 256, g, st);
+  if (can16 && sel && sel[0] == '7')
+    return launch_tiles(gemm_bf16_dma6_kernel<128, 256, 1, 4>, "gemm_bf16_dma6_kernel<128,256,1,4>", "tecm_gemm_bf16/dma6",
+                        (int)((g.M + 127) / 128), (int)((g.N + 255) / 256), 256, g, st);
+  const bool want16 = (sel && !k32) ? (sel[0] == '5' || sel[0] == '8') : true;
+  if (k32 && !can16) return 0;                             // the 64-deep geometries below cannot take K = 32
+  if (can16 && want16) {
+    // tile height: 256 rows, or 288 where that saves a mostly empty last round of blocks on the 256 CUs (N = 768 at
+    // M = 69 864: 819 tiles = 3.2 rounds of 256-row tiles, 729 = 2.85 rounds of 288-row ones); TECM_BF16_DMA = 5 / 8 force one
+    auto cost = [&](int64_t bm) {
+      const int64_t t = ((g.M + bm - 1) / bm) * tiles_n;
+      return ((t + 255) / 256) * bm;
+    };
+    const char* tl = std::getenv("TECM_BF16_TALL");        // "0": never (A/B diagnostics)
+    const bool tall = sel && sel[0] == '8' ? true : ((sel && sel[0] == '5') || (tl && tl[0] == '0') ? false : cost(288) * 100 < cost(DBM) * 95);
+    if (tall)
+      return launch_tiles(gemm_bf16_dma5w_kernel, "gemm_bf16_dma5w_kernel", "tecm_gemm_bf16/dma5w", (int)((g.M + 287) / 288), tiles_n,
+                          D3TH, g, st);
+    return launch_tiles(gemm_bf16_dma5_kernel, "gemm_bf16_dma5_kernel", "tecm_gemm_bf16/dma5", tiles_m, tiles_n, D3TH, g, st);
   }
-  const bool ring = sel && sel[0] == '4';
-  if (ring) {
-    hipLaunchKernelGGL(gemm_bf16_dma4_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(D3TH), 0, st, g, tiles_m, tiles_n);
-    TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma4");
-    tecm_gemm_kernel = "gemm_bf16_dma4_kernel";
-    return 1;
-  }
-  if (sel && sel[0] == '3') {                           // A/B diagnostics: the four-slot ring geometry
-    hipLaunchKernelGGL(gemm_bf16_dma3_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(D3TH), 0, st, g, tiles_m, tiles_n);
-    TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma3");
-    tecm_gemm_kernel = "gemm_bf16_dma3_kernel";
-    return 1;
-  }
-  hipLaunchKernelGGL(gemm_bf16_dma_kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(DNTH), 0, st, g, tiles_m, tiles_n);
-  TECM_CHECK_LAUNCH("tecm_gemm_bf16/dma");
-  tecm_gemm_kernel = "gemm_bf16_dma_kernel";
-  return 1;
+  if (sel && sel[0] == '4')
+    return launch_tiles(gemm_bf16_dma4_kernel, "gemm_bf16_dma4_kernel", "tecm_gemm_bf16/dma4", tiles_m, tiles_n, D3TH, g, st);
+  if (sel && sel[0] == '3')                               // A/B diagnostics: the four-slot ring geometry
+    return launch_tiles(gemm_bf16_dma3_kernel, "gemm_bf16_dma3_kernel", "tecm_gemm_bf16/dma3", tiles_m, tiles_n, D3TH, g, st);
+  return launch_tiles(gemm_bf16_dma_kernel, "gemm_bf16_dma_kernel", "tecm_gemm_bf16/dma", tiles_m, tiles_n, DNTH, g, st);
 }

@@ -807,6 +807,31 @@ __device__ __forceinline__ void block_epilogue16(const TecmGemm& g, f32x16 (&acc
   });
 }
 
+// diagnostics (-DDMA_ABLATE_NOEPI, tools/build_variant.py): what a K loop built without its epilogue ends in instead, so
+// that the accumulators stay live (V: their vector type, 4 or 16 floats)
+template <typename V, int MT, int NT>
+__device__ __forceinline__ void ablate_noepi_sink(const TecmGemm& g, const V (&acc)[MT][NT]) {
+  float keep = 0.f;
+#pragma unroll
+  for (int i = 0; i < MT; ++i)
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+      for (int e = 0; e < (int)(sizeof(V) / sizeof(float)); ++e) keep += acc[i][j][e];
+  if (keep == 12345.678f) reinterpret_cast<float*>(g.C)[0] = keep;
+}
+
+// The launch tail of the LDS-DMA geometries (gemm_bf16_dma.hip, gemm_bf16_p8.hip): one block per tile, the launch checked
+// under the label `what`, `name` recorded for tecm_gemm_last_kernel.  1: the kernel served the call.
+template <typename Kernel>
+int launch_tiles(Kernel kernel, const char* name, const char* what, int tiles_m, int tiles_n, int threads, const TecmGemm& g,
+                 hipStream_t st) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(tiles_m * tiles_n)), dim3(threads), 0, st, g, tiles_m, tiles_n);
+  TECM_CHECK_LAUNCH(what);
+  tecm_gemm_kernel = name;
+  return 1;
+}
+
 template <int ALAY, int BLAY, bool WIN, bool DROP, int ADT = 0, int BDT = 0>      // ADT / BDT: 1 = the operand is bf16 in HBM
 __global__ __launch_bounds__(NTH, 2) void gemm_bf16_kernel(const TecmGemm g, int tiles_m, int tiles_n, int k_chunk) {
   static_assert((ADT == 0 && BDT == 0) || !DROP, "bf16 sources: no prologue dropout");
@@ -825,21 +850,9 @@ __global__ __launch_bounds__(NTH, 2) void gemm_bf16_kernel(const TecmGemm g, int
   __shared__ __attribute__((aligned(16))) unsigned char smem_raw[SMEM_BYTES];
   __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
 
-  // XCD-aware bijective block -> tile map with 8-m-tile groups (see gemm_impl.h)
-  const int nwg = tiles_m * tiles_n;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  constexpr int GROUP_M = 4;
-  const int per_group = GROUP_M * tiles_n;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * per_group;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * BM;
-  const int64_t n0 = (int64_t)tn * BN;
+  const tecm_gemm::TileIdx blk = tecm_gemm::tile_of_block(blockIdx.x, tiles_m, tiles_n, 4);   // 4-m-tile groups
+  const int64_t m0 = (int64_t)blk.tm * BM;
+  const int64_t n0 = (int64_t)blk.tn * BN;
   const int32_t kbeg = blockIdx.z * k_chunk;
   const int32_t kend = min((int32_t)g.K, kbeg + k_chunk);
 

@@ -50,21 +50,10 @@ __global__ __launch_bounds__(tecm_p8::NTH, 1) void gemm_bf16_p8_kernel(const Tec
   static_assert(tecm_p8::BM == 256 && BN == 256 && MT * 16 == 128 && NT * 16 == WTN, "wave tile <= 128 x 64, block tile <= 256 x 256");
   __shared__ __attribute__((aligned(1024))) unsigned char smem_raw[LDS_BYTES];
 
-  // block -> tile map: XCD-contiguous runs, GROUP_M m-tiles per L2 super-tile (as the other geometries)
-  const int nwg = tiles_m * tiles_n;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  const int GROUP_M = g._p1 > 0 ? g._p1 : 4;
-  const int per_group = GROUP_M * tiles_n;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * per_group;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * BM;
-  const int64_t n0 = (int64_t)tn * BN;
+  // block -> tile (gemm_tile_map.h); m-tiles per L2 super-tile: 4, or what ops.GROUP_M sweeps
+  const tecm_gemm::TileIdx blk = tecm_gemm::tile_of_block(blockIdx.x, tiles_m, tiles_n, g._p1 > 0 ? g._p1 : 4);
+  const int64_t m0 = (int64_t)blk.tm * BM;
+  const int64_t n0 = (int64_t)blk.tn * BN;
 
   P8_STAMP(0);
 #ifdef P8_STAMPS
@@ -84,17 +73,8 @@ __global__ __launch_bounds__(tecm_p8::NTH, 1) void gemm_bf16_p8_kernel(const Tec
                             g.a_win.enabled ? g.a_win.N : 0, g.a_win.Lin, g.a_win.Lout, g.a_win.stride_t, g.a_win.Cw};
   tecm_p8::kloop<WR>(o, m0, n0, smem_raw, acc);
 #ifdef DMA_ABLATE_NOEPI                                  // diagnostics (tools/build_variant.py): K loop without the epilogue
-  {
-    float keep = 0.f;
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-      for (int j = 0; j < NT; ++j)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) keep += acc[i][j][e];
-    if (keep == 12345.678f) reinterpret_cast<float*>(g.C)[0] = keep;
-    return;
-  }
+  ablate_noepi_sink(g, acc);
+  return;
 #endif
   P8_STAMP(1);
   __syncthreads();                                      // every wave has left the K loop: the ring becomes staging
@@ -127,14 +107,8 @@ __global__ __launch_bounds__(tecm_p8::NTH, 1) void gemm_bf16_p8_kernel(const Tec
   // masks rows by M only)
   TecmGemm gw = g;
   if constexpr (WR != 128) gw.M = min(g.M, m0 + (int64_t)(wm + 1) * WTM);
-  const int fmode = tecm_gemm::epi_fast_mode(g);         // >= 0: checked on the host (tecm_gemm16_dma_try's can16)
-  constexpr int LPR = WTN / 4, RPI = 64 / LPR;
-  const int lcol = (lane % LPR) * 4, lrow = lane / LPR;
-  const EpiCol ecol = epi_col(g, n0 + wn * WTN + lcol);
-  float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (g.bias) bias4 = *reinterpret_cast<const float4*>(g.bias + (ecol.ok ? ecol.n : 0));   // (lanes outside the matrix: column 0, never stored)
-  tecm_gemm::epi_fast_dispatch<SLABS, 32 / RPI, RPI, STG_LD, true, P8_SPECIAL>(fmode, gw, odc, stg, lrow, lcol, m0 + wm * WTM, ecol, bias4,
-                                                                     stage_slab);
+  // (the mode is >= 0: checked on the host, tecm_gemm16_dma_try's fast_epi)
+  tecm_gemm::epi_fast_tail<SLABS, 32, WTN, true, P8_SPECIAL>(g, gw, odc, stg, lane, m0 + wm * WTM, n0 + wn * WTN, stage_slab);
 #ifdef P8_STAMPS
   P8_STAMP(2);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -199,17 +173,8 @@ int tecm_gemm16_p8_try(const TecmGemm& g, hipStream_t st) {
   const int tiles_n = (int)((g.N + tecm_p8::BN - 1) / tecm_p8::BN);
   const int wr = tecm_p8_rows(g.M, g.N);
   const int tiles_m = (int)((g.M + 2 * wr - 1) / (2 * wr));
-  const dim3 grid((unsigned)(tiles_m * tiles_n)), block(tecm_p8::NTH);
-  if (wr == 128) {
-    hipLaunchKernelGGL(gemm_bf16_p8_kernel<128>, grid, block, 0, st, g, tiles_m, tiles_n);
-    tecm_gemm_kernel = "gemm_bf16_p8_kernel<128>";
-  } else if (wr == 112) {
-    hipLaunchKernelGGL(gemm_bf16_p8_kernel<112>, grid, block, 0, st, g, tiles_m, tiles_n);
-    tecm_gemm_kernel = "gemm_bf16_p8_kernel<112>";
-  } else {
-    hipLaunchKernelGGL(gemm_bf16_p8_kernel<96>, grid, block, 0, st, g, tiles_m, tiles_n);
-    tecm_gemm_kernel = "gemm_bf16_p8_kernel<96>";
-  }
-  TECM_CHECK_LAUNCH("tecm_gemm_bf16/p8");
-  return 1;
+  constexpr const char* what = "tecm_gemm_bf16/p8";
+  if (wr == 128) return launch_tiles(gemm_bf16_p8_kernel<128>, "gemm_bf16_p8_kernel<128>", what, tiles_m, tiles_n, tecm_p8::NTH, g, st);
+  if (wr == 112) return launch_tiles(gemm_bf16_p8_kernel<112>, "gemm_bf16_p8_kernel<112>", what, tiles_m, tiles_n, tecm_p8::NTH, g, st);
+  return launch_tiles(gemm_bf16_p8_kernel<96>, "gemm_bf16_p8_kernel<96>", what, tiles_m, tiles_n, tecm_p8::NTH, g, st);
 }

@@ -98,11 +98,7 @@ void gemm_bf16_tn_kernel(const TnArgs a) {
   __shared__ __attribute__((aligned(1024))) unsigned char smem[TN_ST * STAGE];
 
   // block -> (split, tile): XCD-contiguous runs so that the tiles of one K range meet in one L2
-  const int nwg = a.tiles_m * a.tiles_n * a.splits;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
+  const int wg = tecm_gemm::xcd_contiguous(blockIdx.x, a.tiles_m * a.tiles_n * a.splits);
   const int tiles = a.tiles_m * a.tiles_n;
   const int split = wg / tiles, tile = wg - split * tiles;
   const int tm = tile % a.tiles_m, tn = tile / a.tiles_m;

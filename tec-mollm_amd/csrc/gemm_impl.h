@@ -27,6 +27,7 @@
 // Measured limits and the experiments that did not pay: DESIGN.md section 4, tools/experiments/.
 #pragma once
 #include "common.h"
+#include "gemm_tile_map.h"
 #ifndef TECM_BIG_THREADS
 #define TECM_BIG_THREADS 512
 #endif
@@ -705,15 +706,23 @@ __device__ __forceinline__ void epi_fast_block(const TecmGemm& g, const DropCtx&
 // projection's + wpe), 6 window scatter of C (the patch projection's input gradient); -1: generic loop
 // (Round 5: 5 and 6 were generic-loop cases -- the patch projection forward took 184 us against 87 for the same contraction
 //  with a plain epilogue, its d-input 144 against 83: a store round trip per row group, see "fast epilogue rows" above.)
-__device__ __forceinline__ int epi_fast_mode(const TecmGemm& g) {
+// (host + device: the launchers that serve the straight-line forms only ask it which calls they may take)
+__host__ __device__ __forceinline__ int epi_fast_mode_of(const TecmGemm& g, bool split) {
   if (!(g.io_bf16 & TECM_P0_VEC4)) return -1;
-  if (gridDim.z > 1) return 4;
+  if (split) return 4;
   const int streams = (g.residual ? 1 : 0) + (g.dact_src ? 1 : 0) + (g.accumulate ? 1 : 0);
   if (g.c_win.enabled)                                 // 6: fp32 window scatter with bias / act / dropout, nothing else
     return (streams == 0 && !g.rowbias && !g.preact && !(g.io_bf16 & (TECM_IO_C_BF16 | TECM_IO_PRE_BF16))) ? 6 : -1;
   if (g.rowbias) return streams == 0 ? 5 : -1;        // 5: row bias in place of the input stream
   if (streams > 1) return -1;
   return g.residual ? 1 : (g.dact_src ? 2 : (g.accumulate ? 3 : 0));
+}
+// (the first two tests again, so that gridDim.z is read where it always was: passing `gridDim.z > 1` straight in moves that
+//  load in front of the first test and costs the 16x16 ring kernels two scalar registers)
+__device__ __forceinline__ int epi_fast_mode(const TecmGemm& g) {
+  if (!(g.io_bf16 & TECM_P0_VEC4)) return -1;
+  if (gridDim.z > 1) return 4;
+  return epi_fast_mode_of(g, false);
 }
 // dispatch on the (wave-uniform) mode
 // SPECIAL (the eight-phase bf16 kernel): the four feature combinations of the bf16 training step run branch-free
@@ -741,6 +750,22 @@ __device__ __forceinline__ void epi_fast_dispatch(int mode, const TecmGemm& g, c
   else if (mode == 5) epi_fast_block<SLABS, NIT, RPI, STG_LD, 5, NT>(g, odc, stg, lrow, lcol, mrow0, ecol, bias4, stage);
   else if (mode == 6) epi_fast_block<SLABS, NIT, RPI, STG_LD, 6, NT>(g, odc, stg, lrow, lcol, mrow0, ecol, bias4, stage);
   else epi_fast_block<SLABS, NIT, RPI, STG_LD, 4, NT>(g, odc, stg, lrow, lcol, mrow0, ecol, bias4, stage);
+}
+// The whole straight-line tail of a wave whose SLABS x ROWS staged rows start at (mrow0, ncol0) and are WTN columns wide:
+// the mode, the lane's place in a staged row (float4 per lane, 64 / (WTN / 4) rows per pass), its bias quad, the dispatch.
+// g_rows: the descriptor whose M masks the rows -- g itself, or the eight-phase kernel's copy clamped to its short tile.
+// (One function with the lane values as const locals on purpose: handing them back to the caller, in a struct or through
+//  references, cost the eight-phase kernel's 224-row instance 6 registers and 8 spills.)
+template <int SLABS, int ROWS, int WTN, bool NTS = false, bool SPECIAL = false, typename StageFn>
+__device__ __forceinline__ void epi_fast_tail(const TecmGemm& g, const TecmGemm& g_rows, const DropCtx& odc, const float* stg,
+                                              int lane, int64_t mrow0, int64_t ncol0, StageFn&& stage) {
+  constexpr int LPR = WTN / 4, RPI = 64 / LPR;         // lanes per row, rows per pass
+  const int fmode = epi_fast_mode(g);
+  const int lcol = (lane % LPR) * 4, lrow = lane / LPR;
+  const EpiCol ecol = epi_col(g, ncol0 + lcol);
+  float4 bias4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (g.bias) bias4 = *reinterpret_cast<const float4*>(g.bias + (ecol.ok ? ecol.n : 0));   // (lanes outside the matrix: column 0, never stored)
+  epi_fast_dispatch<SLABS, ROWS / RPI, RPI, WTN + 4, NTS, SPECIAL>(fmode, g_rows, odc, stg, lrow, lcol, mrow0, ecol, bias4, stage);
 }
 
 // ---------------------------------------------------------------------------------------- block epilogue
@@ -845,15 +870,13 @@ __global__ __launch_bounds__(threads_for(BN), (AVEC == 4 && BVEC == 4) ? (thread
   constexpr int SMEM_FLOATS = 2 * TILE_FLOATS > STG_FLOATS ? 2 * TILE_FLOATS : STG_FLOATS;
   __shared__ __attribute__((aligned(16))) float smem[SMEM_FLOATS];
 
-  // XCD-aware, bijective block -> tile map: blocks that share an XCD (id % 8) get a contiguous
-  // run of tiles, n fastest, so an A row-panel is re-read from that XCD's L2.
+  // block -> tile: tile_of_block of gemm_tile_map.h (which explains it), kept inline -- through the shared function six
+  // window + dropout instances of this kernel spill other numbers of scalar registers
   const int nwg = tiles_m * tiles_n;
   const int id = blockIdx.x;
   const int xcd = id & 7, local = id >> 3;
   const int q8 = nwg >> 3, r8 = nwg & 7;
   const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  // grouped order inside the XCD's run: 8 m-tiles x all n-tiles per group, m fastest, so the ~64 blocks
-  // resident on one XCD form an (8 m) x (8 n) super-tile whose A and B panels both live in that XCD's 4 MiB L2
   // m-tiles per group (host-tunable: TecmGemm::_p1).  Default from the measured L2-miss volume:
   // 2 when the matrix is at most 8 tiles wide (N = 768 / 800: 1.3 GB per launch instead of 1.7), 8 otherwise
   const int GROUP_M = g._p1 > 0 ? g._p1 : (tiles_n <= 8 ? 2 : 8);

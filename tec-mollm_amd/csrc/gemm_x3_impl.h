@@ -166,21 +166,9 @@ __global__ __launch_bounds__(NTH, 2) void gemm_x3_kernel(const TecmGemm g, int t
   __shared__ __attribute__((aligned(16))) unsigned char smem_raw[SMEM_BYTES];
   __bf16* smem = reinterpret_cast<__bf16*>(smem_raw);
 
-  // XCD-aware bijective block -> tile map with 4-m-tile groups (see gemm_impl.h)
-  const int nwg = tiles_m * tiles_n;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, local = id >> 3;
-  const int q8 = nwg >> 3, r8 = nwg & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + local;
-  constexpr int GROUP_M = 4;
-  const int per_group = GROUP_M * tiles_n;
-  const int group = wg / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(tiles_m - first_m, GROUP_M);
-  const int in_group = wg - group * per_group;
-  const int tm = first_m + in_group % gsz, tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * BM;
-  const int64_t n0 = (int64_t)tn * BN;
+  const tecm_gemm::TileIdx blk = tecm_gemm::tile_of_block(blockIdx.x, tiles_m, tiles_n, 4);   // 4-m-tile groups
+  const int64_t m0 = (int64_t)blk.tm * BM;
+  const int64_t n0 = (int64_t)blk.tn * BN;
   const int32_t kbeg = blockIdx.z * k_chunk;
   const int32_t kend = min((int32_t)g.K, kbeg + k_chunk);
 

@@ -109,6 +109,48 @@ def test_eight_phase_gemm_tile_height_is_chosen_by_tile_count(built_lib, monkeyp
     assert h.tecm_p8_rows(69864, 3072) == 128          # not a height the kernel is built for: ignored
 
 
+def test_gemm_block_to_tile_map_is_a_bijection(built_lib):
+    """tecm_gemm_tile_of_block / tecm_gemm_tiles_of_blocks are csrc/gemm_tile_map.h compiled for the host -- the map the bf16
+    and split-bf16 GEMM kernels apply to blockIdx.x (the fp32 kernel carries the same formula inline).  For every tiles_m in
+    1..40, tiles_n in 1..12 and group_m in 1..9 (tile counts that are no multiple of the 8 XCDs, tiles_m that is no multiple
+    of group_m, groups taller than the matrix) the ids 0..tiles_m * tiles_n - 1 hit every (tm, tn) exactly once, and the map
+    is the formula the kernels carried inline before the header existed.  One call per configuration fills all its ids; the
+    one-id entry point is compared with it on every id of the group_m = 4 configurations (the kernels' default)."""
+    from tecmollm import _lib
+    one, every = _lib.lib().tecm_gemm_tile_of_block, _lib.lib().tecm_gemm_tiles_of_blocks
+    cfgs = np.stack(np.meshgrid(np.arange(1, 41), np.arange(1, 13), np.arange(1, 10), indexing="ij"), -1).reshape(-1, 3)
+    count = cfgs[:, 0] * cfgs[:, 1]
+    start = np.cumsum(count) - count                                # first flat slot of each configuration
+    total = int(count.sum())
+    which = np.repeat(np.arange(len(cfgs)), count)
+    M, N, G, base = cfgs[which, 0], cfgs[which, 1], cfgs[which, 2], start[which]
+    ids = np.arange(total) - base
+    got_m, got_n = np.full(total, -1, dtype=np.int32), np.full(total, -1, dtype=np.int32)
+    pm, pn = got_m.ctypes.data, got_n.ctypes.data               # each configuration writes its own slots
+    for (m, n, g), s0 in zip(cfgs.tolist(), start.tolist()):
+        every(m, n, g, pm + 4 * s0, pn + 4 * s0)
+    sel = np.flatnonzero(G == 4)
+    one_m, one_n = np.full(sel.size, -1, dtype=np.int32), np.full(sel.size, -1, dtype=np.int32)
+    qm, qn = one_m.ctypes.data, one_n.ctypes.data
+    for _ in map(one, ids[sel].tolist(), M[sel].tolist(), N[sel].tolist(), G[sel].tolist(), range(qm, qm + 4 * sel.size, 4),
+                 range(qn, qn + 4 * sel.size, 4)):
+        pass
+    assert np.array_equal(one_m, got_m[sel]) and np.array_equal(one_n, got_n[sel])
+    # every tile of every configuration exactly once
+    assert (got_m >= 0).all() and (got_m < M).all() and (got_n >= 0).all() and (got_n < N).all()
+    assert (np.bincount(base + got_m * N + got_n, minlength=total) == 1).all()
+    # the formula: XCD-contiguous run, then group_m m-tiles x all n-tiles per group, m fastest
+    nwg = M * N
+    xcd, local, q8, r8 = ids & 7, ids >> 3, nwg >> 3, nwg & 7
+    wg = np.where(xcd < r8, xcd * (q8 + 1), r8 * (q8 + 1) + (xcd - r8) * q8) + local
+    per_group = G * N
+    group = wg // per_group
+    first_m = group * G
+    gsz = np.minimum(M - first_m, G)
+    in_group = wg - group * per_group
+    assert np.array_equal(got_m, first_m + in_group % gsz) and np.array_equal(got_n, in_group // gsz)
+
+
 def test_product_path_refuses_cpu_tensors(built_lib):
     """No CPU fallback: the model raises instead of silently computing somewhere else."""
     from tests.parity import build_model

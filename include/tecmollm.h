@@ -123,6 +123,20 @@ typedef struct TecmGemm {
   int32_t accumulate;
   int32_t split_k;             /* >1: partial sums go to workspace[split][M][N], then reduced */
   float* workspace;            /* >= split_k*M*N floats when split_k > 1 */
+  /* Two optional HINTS (all zero: none).  They promise something about the caller's data; a kernel family may ignore
+   * either (ignoring is always correct), tecm_gemm_f32 honours them where stated and tecm_gemm_last_skipped_flops says
+   * what a call left out.  Both rectangles are periodic in the row: rows with row % period < rows, period > 0.  Both are
+   * honoured only by the plain float4 instances: split_k <= 1, 16-byte friendly operands, no a_win / b_win, no a_drop / b_drop.
+   * Dead output rectangle: the elements of C with row % dead_period < dead_rows and col < dead_cols will never be read.
+   *   A block tile whose rows inside M and whose columns inside N all lie in the rectangle is not computed and NOTHING is
+   *   stored for it (C keeps its previous contents there); tiles on the rectangle's edge are computed whole.  Also
+   *   needs: no c_win, no preact, no TECM_ACT_GELU_ERF (passes that walk all of C or write a second output).
+   * Known-zero A rectangle: A[row][k] is +0 or -0 for row % zero_period < zero_rows and k < zero_k (zero_k a multiple of
+   *   32, below K).  A block tile whose rows inside M all lie in the rectangle starts its K loop at zero_k: the accumulators
+   *   start at +0 and fma(+-0, b, +0) = +0 for finite b, so the result is bit for bit that of the full loop (a non-finite B
+   *   element against such a zero gives NaN in the full loop and is not seen here).  Also needs A stored [m][k]. */
+  int32_t dead_period, dead_rows, dead_cols;
+  int32_t zero_period, zero_rows, zero_k;
 } TecmGemm;
 int tecm_gemm_f32(const TecmGemm* desc, void* stream);
 /* Same contract on the bf16 matrix cores (v_mfma_f32_32x32x16_bf16): operands are rounded to bf16 (RNE) while
@@ -157,6 +171,17 @@ int tecm_p8_rows(int64_t M, int64_t N);
 void tecm_gemm_tile_of_block(int id, int tiles_m, int tiles_n, int group_m, int* tm, int* tn);
 /* The same for every id in 0 .. tiles_m * tiles_n - 1 in one call: tm[id], tn[id]. */
 void tecm_gemm_tiles_of_blocks(int tiles_m, int tiles_n, int group_m, int* tm, int* tn);
+/* The row test behind both hints of TecmGemm, as the kernels apply it to a block tile: 1 when every row r of [r0, r1) has
+ * r % period < rows (period > 0, 0 <= r0 < r1), else 0.  Pure host function (csrc/gemm_tile_map.h compiled for the host). */
+int tecm_gemm_rows_in_rect(int64_t r0, int64_t r1, int32_t period, int32_t rows);
+/* Number of bm x bn block tiles of an M x N matrix that lie wholly inside the periodic rectangle (row % period < rows,
+ * col < cols), counting only a tile's rows inside M and columns inside N: the tiles the dead-rectangle hint skips
+ * (cols = dead_cols) and, with cols = N and bn = N, the row tiles the zero-rectangle hint shortens.  Pure host function. */
+int64_t tecm_gemm_rect_tiles(int64_t M, int64_t N, int32_t bm, int32_t bn, int32_t period, int32_t rows, int64_t cols);
+/* 2 * (multiply-adds) this thread's most recent successful tecm_gemm_* call did NOT issue because it honoured a hint of its
+ * descriptor: over the skipped tiles rows x cols x K, over the shortened ones rows x cols x zero_k, rows and columns counted
+ * inside M and N -- the part of 2 * M * N * K that was not computed.  0 when the call's kernel ignored the hints or none was set.  Pure host function. */
+int64_t tecm_gemm_last_skipped_flops(void);
 /* Name of the contraction kernel (template arguments included, e.g. "gemm_kernel<0,0,4,4,128,false,false,128>") that this
  * thread's most recent successful tecm_gemm_* call launched; the split-K reducer and the erf-GELU pass behind it are not
  * reported.  "" before the first call, unspecified after a failed one.  Host pointer, valid for the life of the library.
@@ -415,6 +440,13 @@ int tecm_attention_fwd(const float* qkv, void* ctx, int32_t io_bf16, int32_t B, 
  * bf16 GEMMs); TECM_ATT_QKV_BF16 -- qkv is the bf16 tensor the forward read; TECM_ATT_DCTX_BF16 -- dctx is bf16 (else fp32). */
 int tecm_attention_bwd(const float* qkv, const float* dctx, void* dqkv, int32_t io_bf16, int32_t B, int32_t T, int32_t N,
                        int32_t heads, int32_t D, const TecmDrop* prob_drop, void* stream);
+/* Query 0 of a causal sequence sees one key: its softmax is 1 whatever q_0 . k_0 is, and its score gradient is 0.  The
+ * kernels with a compile-time T (T = 1, 2, 3, 4, 6, 8, 12) use that: neither the forward nor the backward loads the q
+ * columns of a token-0 row, and the backward writes dq_0 = +0.  (Bit for bit the full arithmetic for finite inputs; a
+ * non-finite q_0 . k_0, which makes the reference NaN, is not seen.)  Returns 0 for such a T -- the caller may then leave
+ * those 64 * heads columns of the token-0 rows unwritten (TecmGemm's dead-rectangle hint) and rely on dq_0 = 0 (its
+ * zero-rectangle hint) -- and 1 for every other T the entry points accept.  Pure host function. */
+int tecm_attention_reads_q0(int32_t T);
 
 /* ------------------------------------------------------------------ reductions / small ops
  * out[s][c] (+)= sum over rows r = o*outer_stride + j (o < outer, j < inner) + seg s offset

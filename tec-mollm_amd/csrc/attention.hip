@@ -67,30 +67,38 @@ __global__ __launch_bounds__(256) void attention_fwd_kernel(const float* __restr
   const int col = h * 64 + sub * 4;
 
   if constexpr (TT > 0) {
+    // Query 0 sees one key: s = q_0 . k_0, exp(s - s) / exp(s - s) = 1 whatever s is (tecm_attention_reads_q0).  q_0 is
+    // not loaded and its row takes p = 1 -- the value the arithmetic below gives for every finite s, bit for bit.
     float4 q[TT], k[TT], v[TT];
+    q[0] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int p = 0; p < TT; ++p) {
       const int64_t r = (row0 + (int64_t)p * N) * ld + col;
-      q[p] = ldq<Q16>(qkv, r);
+      if (p > 0) q[p] = ldq<Q16>(qkv, r);
       k[p] = ldq<Q16>(qkv, r + D);
       v[p] = ldq<Q16>(qkv, r + 2 * D);
     }
 #pragma unroll
     for (int i = 0; i < TT; ++i) {
       float s[TT];
-      float mx = -INFINITY;
+      float inv = 1.0f;
+      if (i == 0) {
+        s[0] = 1.0f;
+      } else {
+        float mx = -INFINITY;
 #pragma unroll
-      for (int j = 0; j <= i; ++j) {
-        s[j] = group16_sum(dot4(q[i], k[j])) * scale;
-        mx = fmaxf(mx, s[j]);
-      }
-      float den = 0.f;
+        for (int j = 0; j <= i; ++j) {
+          s[j] = group16_sum(dot4(q[i], k[j])) * scale;
+          mx = fmaxf(mx, s[j]);
+        }
+        float den = 0.f;
 #pragma unroll
-      for (int j = 0; j <= i; ++j) {
-        s[j] = expf(s[j] - mx);
-        den += s[j];
+        for (int j = 0; j <= i; ++j) {
+          s[j] = expf(s[j] - mx);
+          den += s[j];
+        }
+        inv = 1.0f / den;
       }
-      const float inv = 1.0f / den;
       float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
       for (int j = 0; j <= i; ++j) {
@@ -208,12 +216,16 @@ __device__ __forceinline__ void attention_bwd_body(const float* __restrict__ qkv
   const int64_t row0 = ((int64_t)b * T) * N + n;
   const int col = h * 64 + sub * 4;
   constexpr int TM = TT > 0 ? TT : 32;
+  // Compile-time T: query 0's one probability is 1 and its score gradient ds = 1 * (dp_0 - dp_0) / 8 = +0, so dq_0 = +0 and
+  // dk_0 receives 0 * q_0: q_0 is not loaded, its scores are not formed (tecm_attention_reads_q0; the forward does the same)
+  constexpr bool SKIP0 = TT > 0;
 
   float4 q[TM], k[TM], v[TM], dq[TM], dk[TM], dv[TM];
 #pragma unroll
   for (int p = 0; p < T; ++p) {
     const int64_t r = (row0 + (int64_t)p * N) * ld + col;
-    q[p] = ldq<Q16>(qkv, r);
+    if (SKIP0 && p == 0) q[p] = make_float4(0.f, 0.f, 0.f, 0.f);
+    else q[p] = ldq<Q16>(qkv, r);
     k[p] = ldq<Q16>(qkv, r + D);
     v[p] = ldq<Q16>(qkv, r + 2 * D);
     dq[p] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -223,6 +235,12 @@ __device__ __forceinline__ void attention_bwd_body(const float* __restrict__ qkv
 #pragma unroll
   for (int i = 0; i < T; ++i) {
     const float4 go = ldq<D16>(dctx, (row0 + (int64_t)i * N) * D + col);
+    if (SKIP0 && i == 0) {                             // p_00 = 1: dv_0 += keep * dctx_0; ds = +0, so dq_0 stays +0, dk_0 += 0 * q_0
+      float m = 1.0f;
+      if (dr.thresh) m = tecm_drop_mult(dr.seed, (uint64_t)((item * T) * T), dr.thresh, dr.inv);
+      fma4(dv[0], m, go);
+      continue;
+    }
     float pr[TM], dp[TM];
     float mx = -INFINITY;
 #pragma unroll
@@ -398,6 +416,15 @@ DropA make_dropa(const TecmDrop* d) {
 }
 
 }  // namespace
+
+// 0 for the T both switches below send to a compile-time-T instance (attention_fwd_kernel<TT> / attention_bwd_body<TT>,
+// TT > 0: they leave q_0 alone); 1 for the _kv / _qstream / runtime-T / long-T routes, which read it.
+extern "C" int tecm_attention_reads_q0(int32_t T) {
+  switch (T) {
+    case 1: case 2: case 3: case 4: case 6: case 8: case 12: return 0;
+    default: return 1;
+  }
+}
 
 extern "C" int tecm_attention_fwd(const float* qkv, void* ctxv, int32_t io_bf16, int32_t B, int32_t T, int32_t N,
                                   int32_t heads, int32_t D, const TecmDrop* prob_drop, void* stream) {

@@ -33,6 +33,7 @@ void tecm_set_error(const char* fmt, ...);
 // Name of the contraction kernel this thread's GEMM entry points launched last (tecm_gemm_last_kernel): every launch site
 // stores it next to its launch -- a string literal, or a static built once per template instance.
 extern thread_local const char* tecm_gemm_kernel;
+extern thread_local int64_t tecm_gemm_skipped;      // tecm_gemm_last_skipped_flops: set by gemm_entry (gemm.hip)
 
 static inline bool tecm_aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 

@@ -188,6 +188,32 @@ static int gemm_entry(const TecmGemm* d, void* stream, int mode) {
     gk.dact_src = nullptr;
     gk.out_drop.p = 0.f;
   }
+  // The two hints (tecmollm.h) are served by the fp32 kernel alone; what it cannot honour on this call is zeroed in its
+  // copy of the descriptor, so that the kernel's test is the field itself.  `skipped` is what tecm_gemm_last_skipped_flops
+  // reports: the part of 2 M N K inside the skipped / shortened tiles, in the tile size the dispatch below picks
+  // (gemm_mk_nk.hip / gemm_mk_kn.hip / gemm_km_kn.hip).
+  int64_t skipped = 0;
+  {
+    const bool plain = mode == MODE_F32 && g.split_k <= 1 && avec == 4 && bvec == 4 && !win && !drop;   // the instances that test them
+    const bool dead = plain && g.dead_period > 0 && g.dead_rows > 0 && g.dead_cols > 0 && !g.c_win.enabled && !g.preact && !erf;
+    const bool zero = plain && g.zero_period > 0 && g.zero_rows > 0 && g.zero_k > 0 && g.zero_k % tecm_gemm::BK == 0 &&
+                      g.zero_k < g.K && g.a_layout == TECM_A_MK;
+    if (!dead) gk.dead_period = gk.dead_rows = gk.dead_cols = 0;
+    if (!zero) gk.zero_period = gk.zero_rows = gk.zero_k = 0;
+    const int bn = g.N <= 32 ? 32 : (g.N <= 64 ? 64 : 128);
+    const int bm = (g.a_layout == TECM_A_KM && g.N > 32 && g.M <= 64 && avec == 4 && bvec == 4) ? 64 : tecm_gemm::BM;
+    int64_t dead_n = 0;                                  // columns (inside N) of the column tiles inside dead_cols
+    for (int64_t n0 = 0; dead && n0 < g.N; n0 += bn) {
+      const int64_t n1 = n0 + bn < g.N ? n0 + bn : g.N;
+      if (n1 <= g.dead_cols) dead_n += n1 - n0;
+    }
+    for (int64_t m0 = 0; (dead || zero) && m0 < g.M; m0 += bm) {
+      const int64_t m1 = m0 + bm < g.M ? m0 + bm : g.M;
+      const int64_t gone = dead && tecm_gemm::rows_in_rect(m0, m1, g.dead_period, g.dead_rows) ? dead_n : 0;
+      skipped += 2 * (m1 - m0) * gone * g.K;
+      if (zero && tecm_gemm::rows_in_rect(m0, m1, g.zero_period, g.zero_rows)) skipped += 2 * (m1 - m0) * (g.N - gone) * (int64_t)g.zero_k;
+    }
+  }
   int splits;
   if (mode == MODE_X3 || mode == MODE_X6) {
     splits = tecm_gemm_x3_dispatch(gk, mode == MODE_X6 ? 6 : 3, st);
@@ -223,5 +249,6 @@ static int gemm_entry(const TecmGemm* d, void* stream, int mode) {
                        g.dact_src, g.ldd, g.M, (int32_t)g.N, tecm_gemm::make_drop_host(g.out_drop));
     TECM_CHECK_LAUNCH("tecm_gemm_f32/erf_post");
   }
+  tecm_gemm_skipped = skipped;
   return TECM_OK;
 }

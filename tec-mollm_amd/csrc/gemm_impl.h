@@ -888,7 +888,20 @@ __global__ __launch_bounds__(threads_for(BN), (AVEC == 4 && BVEC == 4) ? (thread
   const int tm = first_m + in_group % gsz, tn = in_group / gsz;
   const int64_t m0 = (int64_t)tm * BMT;
   const int64_t n0 = (int64_t)tn * BN;
-  const int32_t kbeg = blockIdx.z * k_chunk;
+  // The caller's hints (TecmGemm, include/tecmollm.h; gemm_entry has zeroed the ones this launch may not honour): scalar
+  // tests, one per block, in the plain float4 instances only (the window / dropout / narrow-vector ones sit at their
+  // register limits and serve no call that sets a hint).  A tile inside the dead output rectangle leaves before its first
+  // load and stores nothing; a tile whose rows of A are known zeros for k < zero_k starts its K loop there (any multiple of
+  // BK is a stager's kbeg).
+  int32_t kbeg = blockIdx.z * k_chunk;
+  if constexpr (!WIN && !DROP && AVEC == 4 && BVEC == 4) {
+    const int64_t mend = min(m0 + (int64_t)BMT, g.M);
+    if (g.dead_period > 0 && min(n0 + (int64_t)BN, g.N) <= (int64_t)g.dead_cols && rows_in_rect(m0, mend, g.dead_period, g.dead_rows))
+      return;
+    if constexpr (ALAY == TECM_A_MK) {
+      if (g.zero_k > 0 && rows_in_rect(m0, mend, g.zero_period, g.zero_rows)) kbeg = g.zero_k;
+    }
+  }
   const int32_t kend = min((int32_t)g.K, kbeg + k_chunk);
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -43,6 +43,8 @@ class TecmGemm(C.Structure):
         ("residual", c_f32p), ("ldr", C.c_int64),
         ("accumulate", C.c_int32), ("split_k", C.c_int32),
         ("workspace", c_f32p),
+        ("dead_period", C.c_int32), ("dead_rows", C.c_int32), ("dead_cols", C.c_int32),
+        ("zero_period", C.c_int32), ("zero_rows", C.c_int32), ("zero_k", C.c_int32),
     ]
 
 
@@ -235,6 +237,10 @@ EXPORTS = {
     "tecm_gemm_bf16x3": (C.c_int, [C.POINTER(TecmGemm), C.c_void_p]),
     "tecm_gemm_bf16x6": (C.c_int, [C.POINTER(TecmGemm), C.c_void_p]),
     "tecm_gemm_last_kernel": (C.c_char_p, []),
+    "tecm_gemm_last_skipped_flops": (C.c_int64, []),
+    "tecm_gemm_rows_in_rect": (C.c_int, [C.c_int64, C.c_int64, C.c_int32, C.c_int32]),
+    "tecm_gemm_rect_tiles": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64]),
+    "tecm_attention_reads_q0": (C.c_int, [C.c_int32]),
     "tecm_spatial_fwd_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32]),
     "tecm_spatial_bwd_lds_bytes": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "tecm_spatial_fwd": (C.c_int, [C.POINTER(TecmSpatial), C.c_void_p]),

@@ -32,6 +32,14 @@ def _split_dcattn() -> bool:
     return os.environ.get("TECM_SPLIT_DCATTN", "1") != "0"
 
 
+def _causal_q0(T: int, prec) -> bool:
+    """Causal attention gives query 0 one key: its softmax is 1 and dq_0 = 0 whatever q_0 is.  True where the attention
+    kernels for this T leave q_0 alone (ops.attention_reads_q0) and the GEMMs are the fp32 ones: the c_attn forward then
+    skips the tiles that would compute q_0 (rows (b T + 0) N + n, the first D columns) and the d c_attn launches the K range
+    that multiplies dq_0 = 0.  TECM_CAUSAL_Q0=0 switches both hints off (A/B diagnostics); bf16 mode sets none."""
+    return os.environ.get("TECM_CAUSAL_Q0", "1") != "0" and int(prec) == ops.PREC_FP32 and not ops.attention_reads_q0(T)
+
+
 def _ln_batch_reduce() -> bool:
     """TECM_LN_BATCH_REDUCE=0: every LayerNorm backward of the GPT-2 stack reduces its own partials (A/B diagnostics)."""
     return os.environ.get("TECM_LN_BATCH_REDUCE", "1") != "0"
@@ -868,7 +876,9 @@ class GPT2StackFn(torch.autograd.Function):
         # bf16 mode: qkv is written as bf16 by the c_attn GEMM (what a Linear's output is under autocast) and read as
         # such by the attention kernels, forward and backward: 644 -> 322 MB per layer, three times over
         qkv = torch.empty(M, F3, device=h.device, dtype=torch.bfloat16 if (a16 and QKV16) else torch.float32)
-        gemm(M, F3, KE, u16 if a16 else u, KE, wcatT, KE, qkv, F3, b_layout=B_NK, bias=bqkv, bf16=plan.bf16)
+        # (fp32: the q columns of the token-0 rows are left unwritten where the attention kernels never read them)
+        q0 = (T * N, N, D) if _causal_q0(T, plan.bf16) else None
+        gemm(M, F3, KE, u16 if a16 else u, KE, wcatT, KE, qkv, F3, b_layout=B_NK, bias=bqkv, bf16=plan.bf16, dead_rect=q0)
         if not keep:
             u = u16 = None
         cx = torch.empty(M, D, device=h.device, dtype=torch.bfloat16 if a16 else torch.float32)
@@ -1002,14 +1012,16 @@ class GPT2StackFn(torch.autograd.Function):
             ops.attention_bwd(qkv, dcx, dqkv, B, T, N, GPT_HEADS, D, plan.spec(site_attn(i), 1))
             u16g = g16 and q16 and u.dtype == torch.bfloat16
             du = torch.empty(M, KE, device=dh.device, dtype=torch.bfloat16 if u16g else torch.float32)   # [ d LN1-out | dz ]
+            # fp32: dq_0 -- the first D of the F3 values of k in the token-0 rows -- is exactly zero (see _causal_q0)
+            q0 = (T * N, N, D) if _causal_q0(T, plan.bf16) else None
             if int(plan.bf16) == ops.PREC_FP32 and _split_dcattn():
                 # fp32: N = 800 is 7 tile columns of 128 with 96 of the last 128 dead.  The 768 base columns run as six full
                 # tile columns, the 32 LoRA columns (dz) as a launch of the 32-wide tile on a second read of dqkv; every
                 # element is the same sum over k in the same order
-                gemm(M, D, F3, dqkv, F3, wcat, F3, du, KE, bf16=plan.bf16)
-                gemm(M, LORA_R, F3, dqkv, F3, wcat, F3, du, KE, b_off=D * F3, c_off=D, bf16=plan.bf16)
+                gemm(M, D, F3, dqkv, F3, wcat, F3, du, KE, bf16=plan.bf16, zero_rect=q0)
+                gemm(M, LORA_R, F3, dqkv, F3, wcat, F3, du, KE, b_off=D * F3, c_off=D, bf16=plan.bf16, zero_rect=q0)
             else:
-                gemm(M, KE, F3, dqkv, F3, wcat, F3, du, KE, bf16=plan.bf16)
+                gemm(M, KE, F3, dqkv, F3, wcat, F3, du, KE, bf16=plan.bf16, zero_rect=q0)
             lspec = plan.spec(site_lora(i), KE)
             dlB = _empty(F3, LORA_R, like=dh)
             gemm(F3, LORA_R, M, dqkv, F3, u, KE, dlB, LORA_R, a_layout=A_KM, b_layout=B_KN, b_off=D,

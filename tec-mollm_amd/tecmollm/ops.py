@@ -57,7 +57,8 @@ def gemm(M: int, N: int, K: int, A: torch.Tensor, lda: int, B: torch.Tensor, ldb
          rowbias: Optional[Tuple[torch.Tensor, int, int, int]] = None,
          preact: Optional[Tuple[torch.Tensor, int]] = None, dact_src: Optional[Tuple[torch.Tensor, int]] = None,
          residual: Optional[Tuple[torch.Tensor, int]] = None, accumulate: bool = False, split_k: int = 1,
-         bf16: bool = False) -> None:
+         bf16: bool = False, dead_rect: Optional[Tuple[int, int, int]] = None,
+         zero_rect: Optional[Tuple[int, int, int]] = None) -> None:
     # A / B / Cout may be torch.bfloat16 tensors (bf16 mode only, plain MK x NK): operands that already live in HBM as
     # bf16 (activations rounded once by their producer, cached bf16 weights) and / or a bf16 output for such a consumer
     """C[M,N] = epilogue(alpha * A_view[M,K] . B_view[K,N]); see TecmGemm in include/tecmollm.h.
@@ -69,7 +70,10 @@ def gemm(M: int, N: int, K: int, A: torch.Tensor, lda: int, B: torch.Tensor, ldb
     bf16=True asks for the bf16 matrix cores (operands rounded to bf16, fp32 accumulate); calls the bf16
     kernel cannot serve (N < 64 output columns or operands that are not 16-byte friendly) run on the exact
     fp32 kernel instead -- the choice is a pure function of shapes/alignment (`uses_bf16`), never silent:
-    with timing on, every record carries the name of the kernel the library launched (tecm_gemm_last_kernel)."""
+    with timing on, every record carries the name of the kernel the library launched (tecm_gemm_last_kernel).
+    dead_rect = (period, rows, cols) and zero_rect = (period, rows, k) are TecmGemm's two hints: elements of C nobody will
+    read, and a rectangle of A known to hold zeros.  Promises about the caller's data that a kernel may use or ignore; the
+    timing records count the flops the call issued (2 M N K less tecm_gemm_last_skipped_flops)."""
     g = TecmGemm()
     g.M, g.N, g.K = M, N, K
     io = (IO_A_BF16 if A.dtype == torch.bfloat16 else 0) | (IO_B_BF16 if B.dtype == torch.bfloat16 else 0) | \
@@ -105,6 +109,10 @@ def gemm(M: int, N: int, K: int, A: torch.Tensor, lda: int, B: torch.Tensor, ldb
         g.residual, g.ldr = residual[0].data_ptr(), residual[1]
     g.accumulate = 1 if accumulate else 0
     g._p1 = GROUP_M
+    if dead_rect is not None:
+        g.dead_period, g.dead_rows, g.dead_cols = dead_rect
+    if zero_rect is not None:
+        g.zero_period, g.zero_rows, g.zero_k = zero_rect
     ws = None
     if split_k > 1:
         ws = torch.empty(split_k * M * N, device=Cout.device, dtype=torch.float32)
@@ -137,7 +145,7 @@ def gemm(M: int, N: int, K: int, A: torch.Tensor, lda: int, B: torch.Tensor, ldb
     for t in (preact, dact_src, residual):
         if t is not None:
             nbytes += M * N * t[0].element_size()
-    _timing.append((name, 2.0 * M * N * K, e0, e1, float(nbytes)))
+    _timing.append((name, 2.0 * M * N * K - float(lib().tecm_gemm_last_skipped_flops()), e0, e1, float(nbytes)))
 
 
 PREC_FP32, PREC_BF16, PREC_BF16X3, PREC_BF16X6 = 0, 1, 2, 3
@@ -413,6 +421,12 @@ def attention_bwd(qkv: torch.Tensor, dctx: torch.Tensor, dqkv: torch.Tensor, B: 
         (ATT_DCTX_BF16 if dctx.dtype == torch.bfloat16 else 0)
     check(lib().tecm_attention_bwd(qkv.data_ptr(), dctx.data_ptr(), dqkv.data_ptr(), io, B, T, N, heads, D, C.byref(pd),
                                    stream_ptr()), "tecm_attention_bwd")
+
+
+def attention_reads_q0(T: int) -> bool:
+    """Do the attention kernels for T tokens read the query of token 0?  (No for the compile-time-T instances: that row's
+    softmax is 1 and its score gradient 0 whatever q_0 is, so nobody has to compute q_0 and dq_0 is exactly zero.)"""
+    return bool(lib().tecm_attention_reads_q0(T))
 
 
 def colsum(inp: torch.Tensor, ld: int, outer: int, inner: int, nseg: int, Cn: int, *, in_off: int = 0,

@@ -355,6 +355,13 @@ int tecm_gn_y16_supported(int32_t L, int32_t N, int32_t Cout);
  * only ones that serve act_stride > 1): L * 3*Cout/4 quads in whole rounds of 4 or 8 waves, at most 9 per lane.  Pure host
  * function. */
 int tecm_gn_reg_supported(int32_t L, int32_t N, int32_t Cout);
+/* The kernel tecm_groupnorm_gelu_fwd / _bwd launches for these arguments and 16-byte aligned tensors, with its template
+ * arguments -- "gn_gelu_fwd_reg<1,4,9,false>", "gn_bwd_sums16_kernel<2>+gn_bwd_apply16_kernel<2>" -- or "" where the
+ * launcher refuses.  has_seq_sums: the backward call passes a seq_sums workspace.  The answers come from the functions the
+ * launchers route by (the environment switches TECM_GN_BWD_SPLIT / TECM_GN_BWD_WPS included).  Pure host functions; the
+ * string lives until this thread's next call of either. */
+const char* tecm_gn_fwd_path(int32_t L, int32_t N, int32_t Cout, int32_t io_bf16, int32_t act_stride);
+const char* tecm_gn_bwd_path(int32_t L, int32_t N, int32_t Cout, int32_t io_bf16, int32_t has_seq_sums);
 /* act_stride s >= 1: only the time steps t % s == 0 are written, into a COMPACT (B, ceil(L / s), N, CT) tensor -- the
  * stride-s 1x1 conv behind the block (modules.py:36-41) reads nothing else; the statistics cover every step.  s > 1 is
  * served by the register-resident kernels only (TECM_E_ARG otherwise: callers ask tecm_gn_reg_supported first). */

@@ -258,6 +258,8 @@ EXPORTS = {
                                           C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
     "tecm_gn_y16_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     "tecm_gn_reg_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
+    "tecm_gn_fwd_path": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tecm_gn_bwd_path": (C.c_char_p, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "tecm_groupnorm_gelu_bwd": (C.c_int, [c_f32p, C.c_int32, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
                                           C.POINTER(C.c_int32), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, c_f32p, C.c_void_p]),

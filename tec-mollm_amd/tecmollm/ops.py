@@ -332,11 +332,25 @@ GN_Y_BF16, GN_OUT_BF16, GN_DACT_BF16 = 1, 2, 4
 
 
 def gn_reg_ok(L: int, N: int, Cout: int) -> bool:
-    """True when the register-resident GroupNorm+GELU kernels (csrc/norm.hip: gn_reg_pairs with 4 or 8 waves per sequence,
-    at most 9 float4 per lane) serve BOTH directions -- the only kernels that read / write bf16 activations.  Longer
-    sequences (the reference's default L_in = 336) take the multi-pass fp32 kernels, and the conv block then keeps its
-    activations fp32 in bf16 mode too."""
+    """True when the register-resident GroupNorm+GELU kernels (csrc/groupnorm.hip: gn_reg_pairs with 4 or 8 waves per
+    sequence, at most 9 float4 per lane) serve BOTH directions -- the only kernels that read / write bf16 activations.
+    Longer sequences (the reference's default L_in = 336) take the multi-pass fp32 kernels, and the conv block then keeps
+    its activations fp32 in bf16 mode too."""
     return lib().tecm_gn_reg_supported(L, N, Cout) == 1
+
+
+def gn_fwd_path(L: int, N: int, Cout: int, io_bf16: int = 0, act_stride: int = 1) -> str:
+    """The kernel groupnorm_gelu_fwd launches for these arguments (io_bf16: GN_* flags) and aligned tensors, with its
+    template arguments; "" where the library refuses the call.  Pure host arithmetic."""
+    return lib().tecm_gn_fwd_path(L, N, Cout, io_bf16, act_stride).decode()
+
+
+def gn_bwd_path(L: int, N: int, Cout: int, io_bf16: int = 0, has_seq_sums: Optional[bool] = None) -> str:
+    """The same for groupnorm_gelu_bwd.  has_seq_sums: the call hands the library a workspace for the per-sequence sums;
+    None: as groupnorm_gelu_bwd does (whenever y is bf16)."""
+    if has_seq_sums is None:
+        has_seq_sums = bool(io_bf16 & GN_Y_BF16)
+    return lib().tecm_gn_bwd_path(L, N, Cout, io_bf16, 1 if has_seq_sums else 0).decode()
 
 
 def _gn_io(y: torch.Tensor, out: torch.Tensor) -> int:

@@ -400,7 +400,7 @@ def ln_run(ops, rng, dev, shape, insts=("plain",)):
     return entries, extras, names
 
 
-# name (the family norm.hip dispatches it to): ((Bn, L, N, Cout, stride), all-bf16 tensors, the family of sequence 0).
+# name (the family groupnorm.hip dispatches it to): ((Bn, L, N, Cout, stride), all-bf16 tensors, the family of sequence 0).
 # Sequence s is of family NORM_FAMILIES[(start + s) % 7]; every start is chosen so that the launch holds an `offset`
 # sequence (|mean| >> std: what a one-pass variance gets wrong) and a `constant` one (zero variance) -- with three
 # sequences that is (constant, onehot, offset), start 5.  tests/test_host_hard_inputs.py asserts it.

@@ -55,7 +55,7 @@ def test_layernorm_on_hard_rows(dev, shape):
 # ------------------------------------------------------------------------------------------------ GroupNorm(1) + GELU
 @pytest.mark.parametrize("name", list(HI.GN_SHAPES))
 def test_groupnorm_gelu_on_hard_sequences(dev, name):
-    """One shape per kernel family of csrc/norm.hip (generic, 4- and 8-wave register, Cout = 256, the all-bf16 kernels, Cout =
+    """One shape per kernel family of csrc/groupnorm.hip (generic, 4- and 8-wave register, Cout = 256, the all-bf16 kernels, Cout =
     256 among them), every sequence of the launch of another family, an `offset` and a `constant` one in every launch, the
     three branches of an offset sequence at different offsets: act, (mean,
     rstd), dy, dgamma, dbeta, colsum(dy).  The all-bf16 kernels' act / dy: one bf16 ulp plus the bar on the group's scale."""

@@ -393,13 +393,23 @@ def test_layernorm_bwd_adds_a_masked_second_gradient_stream(dev, M, dt):
 
 
 # register-resident kernels: 4 waves/sequence (2304 quads), 8 waves (4608 quads: L_in = 96), forward-only 2 waves
-# (1152 quads, odd sequence count), Cout = 256; (2, 6, 3, 64, 1) and the backward of the 2-wave case take the
-# generic multi-pass kernels
+# (1152 quads, odd sequence count: a dead wave in the last two-sequence block); the backward of the 2-wave cases and the
+# sequences that fill no round of lanes take the generic multi-pass kernels (three sequences: three trips round one block's
+# grid-stride loop).  Every CPB (Cout / 64) of every fp32-y kernel template is reached, and asserted to be.
+_GN_F32_PATHS = {       # (L, Cout): the suffixes of gn_gelu_fwd_ / gn_gelu_bwd_ the shape reaches
+    (48, 64): ("reg<1,4,9,false>", "reg<1,4,9,false,false,false>"), (24, 128): ("reg<2,4,9,false>", "reg<2,4,9,false,false,false>"),
+    (12, 256): ("reg<4,4,9,false>", "reg<4,4,9,false,false,false>"), (96, 64): ("reg<1,8,9,false>", "reg<1,8,9,false,false,false>"),
+    (48, 128): ("reg<2,8,9,false>", "reg<2,8,9,false,false,false>"), (24, 256): ("reg<4,8,9,false>", "reg<4,8,9,false,false,false>"),
+    (24, 64): ("reg<1,2,18,false>", "kernel<1>"), (12, 128): ("reg<2,2,18,false>", "kernel<2>"), (6, 256): ("reg<4,2,18,false>", "kernel<4>"),
+    (6, 64): ("kernel<1>", "kernel<1>"), (6, 128): ("kernel<2>", "kernel<2>"), (5, 256): ("kernel<4>", "kernel<4>")}
 @pytest.mark.parametrize("Bn,L,N,Cout,stride", [(2, 48, 5, 64, 2), (1, 24, 9, 128, 2), (2, 6, 3, 64, 1),
                                                 (1, 96, 3, 64, 2), (1, 48, 3, 128, 1), (1, 24, 3, 64, 2),
-                                                (1, 12, 3, 256, 2)])
+                                                (1, 12, 3, 256, 2), (1, 6, 3, 128, 1), (1, 5, 3, 256, 2),
+                                                (1, 12, 3, 128, 2), (1, 6, 3, 256, 1), (1, 24, 3, 256, 2)])
 def test_groupnorm_gelu_fwd_bwd(dev, Bn, L, N, Cout, stride):
     from tecmollm import ops
+    fwd, bwd = _GN_F32_PATHS[(L, Cout)]
+    assert ops.gn_fwd_path(L, N, Cout) == "gn_gelu_fwd_" + fwd and ops.gn_bwd_path(L, N, Cout) == "gn_gelu_bwd_" + bwd
     CT = 3 * Cout
     y = _rand(Bn, L, N, CT, dev=dev, seed=1)
     g, b = 1 + 0.1 * _rand(CT, dev=dev, seed=2), 0.1 * _rand(CT, dev=dev, seed=3)
@@ -430,8 +440,15 @@ def test_groupnorm_gelu_fwd_bwd(dev, Bn, L, N, Cout, stride):
 def test_groupnorm_gelu_compact_strided_act_and_bf16_dact(dev, Bn, L, N, Cout, stride):
     """act_stride = s: only the time steps the stride-s 1x1 conv reads (modules.py:36-41) are written, into a compact
     (B, ceil(L / s), N, CT) tensor, bit-identical to those rows of the full activation; the statistics still cover every
-    step.  Backward: a bf16 dact (TECM_GN_DACT_BF16) gives the result of the fp32 kernel fed the same rounded values."""
+    step.  Backward: a bf16 dact (TECM_GN_DACT_BF16) gives the result of the fp32 kernel fed the same rounded values.
+    Only the register-resident kernels serve either: 8 waves per sequence at L = 96, else 4."""
     from tecmollm import TecmError, ops
+    reg = f"reg<{Cout // 64},{8 if L == 96 else 4},9,"
+    for s in (1, stride):
+        assert ops.gn_fwd_path(L, N, Cout, 0, s) == f"gn_gelu_fwd_{reg}false>"
+        assert ops.gn_fwd_path(L, N, Cout, ops.GN_OUT_BF16, s) == f"gn_gelu_fwd_{reg}true>"
+    assert ops.gn_bwd_path(L, N, Cout, ops.GN_OUT_BF16 | ops.GN_DACT_BF16) == f"gn_gelu_bwd_{reg}true,true,false>"
+    assert ops.gn_bwd_path(L, N, Cout, ops.GN_OUT_BF16) == f"gn_gelu_bwd_{reg}true,false,false>"
     CT = 3 * Cout
     y = _rand(Bn, L, N, CT, dev=dev, seed=1)
     g, b = 1 + 0.1 * _rand(CT, dev=dev, seed=2), 0.1 * _rand(CT, dev=dev, seed=3)
@@ -454,15 +471,33 @@ def test_groupnorm_gelu_compact_strided_act_and_bf16_dact(dev, Bn, L, N, Cout, s
         ops.groupnorm_gelu_bwd(d16, stride, y, g, b, st, torch.empty(Bn, L, N, CT, device=dev), Bn, L, N, Cout)   # bf16 dact, fp32 dy
 
 
+_GN_SPLIT = "gn_bwd_sums16_kernel<{0}>+gn_bwd_apply16_kernel<{0}>"
+_GN_Q16 = "gn_gelu_bwd_reg<{},{},9,true,true,true>"
+_GN_Y16_PATHS = {       # (L, Cout): forward, backward with the workspace ops hands over, backward with TECM_GN_BWD_SPLIT=0
+    (48, 64): ("gn_gelu_fwd_reg16<1,3>", _GN_SPLIT.format(1), _GN_Q16.format(1, 4)),
+    (24, 128): ("gn_gelu_fwd_reg16<2,3>", _GN_SPLIT.format(2), _GN_Q16.format(2, 4)),
+    (96, 64): ("gn_gelu_fwd_reg16<1,6>", _GN_SPLIT.format(1), _GN_Q16.format(1, 8)),
+    (48, 128): ("gn_gelu_fwd_reg16<2,6>", _GN_SPLIT.format(2), _GN_Q16.format(2, 8)),
+    (16, 64): ("gn_gelu_fwd_reg16<1,3>", _GN_SPLIT.format(1), _GN_Q16.format(1, 4)),
+    (12, 256): ("gn_gelu_fwd_reg16<4,3>", _GN_Q16.format(4, 4), _GN_Q16.format(4, 4)),       # the pair serves Cout 64 / 128
+    (40, 64): ("gn_gelu_fwd_reg16<1,3>", _GN_SPLIT.format(1), "gn_gelu_bwd_reg16<1,3>"),
+    (24, 256): ("gn_gelu_fwd_reg16<4,6>", _GN_Q16.format(4, 8), _GN_Q16.format(4, 8))}
 @pytest.mark.parametrize("Bn,L,N,Cout,stride", [(2, 48, 5, 64, 2), (1, 24, 9, 128, 2), (1, 96, 3, 64, 2), (1, 48, 3, 128, 2),
-                                                (2, 16, 7, 64, 1), (1, 12, 3, 256, 2), (1, 40, 3, 64, 2)])
-def test_groupnorm_gelu_all_bf16_kernels(dev, Bn, L, N, Cout, stride):
+                                                (2, 16, 7, 64, 1), (1, 12, 3, 256, 2), (1, 40, 3, 64, 2), (1, 24, 3, 256, 2)])
+def test_groupnorm_gelu_all_bf16_kernels(dev, monkeypatch, Bn, L, N, Cout, stride):
     """TECM_GN_Y_BF16: y, act, dact and dy all bf16 (a lane's unit is 8 channels = one 16-byte access), statistics and
     arithmetic fp32 -- against the fp32-y kernels fed the same rounded y (outputs one bf16 ulp, statistics and parameter
     gradients 1e-5: other lanes sum other elements) and against fp64 GroupNorm(1) + GELU (modules.py:28-29) of that y.
-    Sequences that fill the last round of lanes only partly (L = 48 x 24 octs over 256 lanes: 4.5 per lane; L = 40)."""
+    Sequences that fill the last round of lanes only partly (L = 48 x 24 octs over 256 lanes: 4.5 per lane; L = 40).
+    The backward runs twice: with the workspace for the per-sequence sums (the streaming pair where it serves Cout) and
+    with TECM_GN_BWD_SPLIT=0 (the sequence-resident kernels)."""
     from tecmollm import ops
     CT = 3 * Cout
+    ALL16 = ops.GN_Y_BF16 | ops.GN_OUT_BF16 | ops.GN_DACT_BF16
+    monkeypatch.delenv("TECM_GN_BWD_SPLIT", raising=False)
+    monkeypatch.delenv("TECM_GN_BWD_WPS", raising=False)
+    fwd_path, bwd_split, bwd_resident = _GN_Y16_PATHS[(L, Cout)]
+    assert ops.gn_fwd_path(L, N, Cout, ops.GN_Y_BF16 | ops.GN_OUT_BF16, stride) == fwd_path
     assert ops.gn_y16_ok(L, N, Cout)
     y16 = _rand(Bn, L, N, CT, dev=dev, seed=1).bfloat16()
     y = y16.float()
@@ -486,20 +521,24 @@ def test_groupnorm_gelu_all_bf16_kernels(dev, Bn, L, N, Cout, stride):
     ref = torch.cat(outs, 1).view(Bn, N, CT, L).permute(0, 3, 1, 2)
     assert _rel(a16, ref[:, ::stride]) < 5e-3                     # bf16 output
     dact16 = _rand(Bn, La, N, CT, dev=dev, seed=4).bfloat16()
-    dy16 = torch.full((Bn, L, N, CT), float("nan"), device=dev, dtype=torch.bfloat16)
     dyq = torch.empty(Bn, L, N, CT, device=dev, dtype=torch.bfloat16 if quad else torch.float32)
-    r16 = ops.groupnorm_gelu_bwd(dact16, stride, y16, g, b, st16, dy16, Bn, L, N, Cout)
     rq = ops.groupnorm_gelu_bwd(dact16 if quad else dact16.float(), stride, y, g, b, st16, dyq, Bn, L, N, Cout)
     dyq = dyq.bfloat16()
-    assert torch.isfinite(dy16.float()).all()
-    d = (dy16.float() - dyq.float()).abs()
-    assert bool((d <= dyq.float().abs() * 2.0 ** -7 + 1e-5 * float(dyq.float().abs().max())).all())
-    for a_, b_ in zip(r16, rq):
-        assert _rel(a_, b_) < 2e-5
     fullg = torch.zeros(Bn, L, N, CT, dtype=torch.float64, device=dev)
     fullg[:, ::stride] = dact16.double()
     gy, gg, gb = torch.autograd.grad(ref, (yd, gd, bd), fullg)
-    assert _rel(dy16, gy) < 5e-3 and _rel(r16[0], gg) < TOL and _rel(r16[1], gb) < TOL
+    for split, bwd_path in ((True, bwd_split), (False, bwd_resident)):
+        if not split:
+            monkeypatch.setenv("TECM_GN_BWD_SPLIT", "0")
+        assert ops.gn_bwd_path(L, N, Cout, ALL16) == bwd_path
+        dy16 = torch.full((Bn, L, N, CT), float("nan"), device=dev, dtype=torch.bfloat16)
+        r16 = ops.groupnorm_gelu_bwd(dact16, stride, y16, g, b, st16, dy16, Bn, L, N, Cout)
+        assert torch.isfinite(dy16.float()).all()
+        d = (dy16.float() - dyq.float()).abs()
+        assert bool((d <= dyq.float().abs() * 2.0 ** -7 + 1e-5 * float(dyq.float().abs().max())).all())
+        for a_, b_ in zip(r16, rq):
+            assert _rel(a_, b_) < 2e-5
+        assert _rel(dy16, gy) < 5e-3 and _rel(r16[0], gg) < TOL and _rel(r16[1], gb) < TOL
     with pytest.raises(Exception):
         ops.groupnorm_gelu_bwd(dact16.float(), stride, y16, g, b, st16, dy16, Bn, L, N, Cout)      # bf16 y, fp32 dact
 
@@ -692,6 +731,8 @@ def test_gn_kernels_accept_bf16_tensors_exactly_where_tecm_gn_reg_supported_says
     st = torch.empty(Bn * N, 3, 2, device=dev)
     dact = _rand(Bn, (L + 1) // 2, N, CT, dev=dev, seed=4)
     dy16 = torch.empty_like(act16)
+    served = ops.gn_fwd_path(L, N, Cout, ops.GN_OUT_BF16) != "" and ops.gn_bwd_path(L, N, Cout, ops.GN_OUT_BF16) != ""
+    assert served == ops.gn_reg_ok(L, N, Cout)
     if ops.gn_reg_ok(L, N, Cout):
         ops.groupnorm_gelu_fwd(y, g, b, act16, st, Bn, L, N, Cout)
         ops.groupnorm_gelu_bwd(dact, 2, y, g, b, st, dy16, Bn, L, N, Cout)

@@ -4,6 +4,9 @@ library that `TECM_LIB=<path>` selects (tecmollm/_lib.py):
 
     python tools/build_variant.py spatial_fwd.hip stamps -DSPF_STAMPS
     TECM_LIB=tec-mollm_amd/tecmollm/variants/libtecmollm_hip_stamps.so python tools/spatial_bench.py
+
+    python tools/build_variant.py groupnorm.hip nodgelu -DGN_ABLATE_DGELU      # every GroupNorm backward (csrc/gn_math.h)
+    TECM_LIB=tec-mollm_amd/tecmollm/variants/libtecmollm_hip_nodgelu.so MODE=y16 python tools/gn_bench.py
 """
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -745,6 +745,94 @@ typedef struct {
 } TecmEnsemble;
 int tecm_ensemble_stats(const TecmEnsemble* e, void* stream);
 
+/* (3g) split-conformal prediction intervals: nonconformity scores of a calibration split into a score store (a), the exact
+ * k-th smallest score of every (group, cell) of that store (b), and the intervals those quantiles give, scored on a split or
+ * emitted for a forecast (c).  Prediction and truth go through the value pipeline of (3) / (3b) (non-finite scaled prediction
+ * -> 0, inverse transform with two f32 roundings, nan_to_num, optional clip of the prediction only), which leaves float32 p
+ * and y; with w = max(sigma, sigma_min) (sigma: an optional per-sample scale in PHYSICAL units, e.g. an ensemble's std; a NaN
+ * sigma counts as sigma_min) the score is, in float32 (csrc/conformal_score.h, ONE function for (a) and (c)),
+ *   TECM_CONF_ABS:     r = |y - p|          TECM_CONF_SIGNED:  r = y - p          with sigma:  r = r / w  (one IEEE division).
+ * Operands are addressed as base[s*stride_s + h*stride_h + i*stride_i] (element strides, 64-bit) and read in place; lanes run
+ * along the nodes.
+ *
+ * (a) tecm_conformal_scores: scores[(row0 + s)*ld + h*I + i] = r(s, h, i), float32, ld >= H*I; rows outside
+ *     [row0, row0 + S) and columns at or beyond H*I are not touched. */
+#define TECM_CONF_ABS 0
+#define TECM_CONF_SIGNED 1
+#define TECM_INTERVAL_STATS 6
+#define TECM_SELECT_MAX_Q 8
+typedef struct {
+  const float* pred; int64_t p_stride_s, p_stride_h, p_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  const float* sigma; int64_t g_stride_s, g_stride_h, g_stride_i;     /* NULL: no scale (w = 1) */
+  int64_t S; int32_t H; int32_t mode; int64_t I;       /* samples, horizons, TECM_CONF_*, nodes */
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  float sigma_min;                                      /* > 0 when sigma is given */
+  float* scores; int64_t ld; int64_t row0;
+} TecmConformalScores;
+int tecm_conformal_scores(const TecmConformalScores* c, void* stream);
+
+/* (b) tecm_column_select: out[(q*G + g)*C + c] = the ranks[g*Q + q]-th smallest (1-based) of { x[s*ld + c] : group[s] == g },
+ *     for a row-major float32 store x (S, C) with leading dimension ld >= C.  A rank <= 0 gives -inf, a rank above the number
+ *     of rows of the group (an empty group included) +inf; otherwise the output is the value of an actual element of exactly
+ *     that rank in the numeric order with -0 and +0 adjacent and every NaN (of either sign) after +inf -- numpy's sort order.
+ *     A NaN that is selected comes back as the quiet NaN 0x7fffffff.
+ *   group  (S) int32 or NULL (every row in group 0); a row whose id is outside [0, G) belongs to no group and sets
+ *          TECM_BAD_GROUP in *err_flag, never clamped.
+ *   ranks  (G, Q) int32 on the device.
+ *     Exact and bit-reproducible: a four-pass most-significant-digit radix select on 8-bit digits of the monotone key (all
+ *     bits of a negative flipped, the sign bit of a non-negative set, NaN -> 0xffffffff) with integer counts only.  One block
+ *     of sixteen waves serves 64 neighbouring columns of one (group, rank): lanes run along the columns, so a row is one
+ *     coalesced 256-B read; the waves share the rows and count into one [256][64] uint32 histogram in LDS with LDS integer
+ *     adds (lane-contiguous: a wave's update has no bank conflict); after each pass every wave walks the bins of its lane's
+ *     column to the digit holding the rank.  The group id of a row is wave-uniform, so rows of other groups are not loaded.
+ *     Limits: 0 < S < 2^31, 1 <= Q <= TECM_SELECT_MAX_Q, 1 <= G <= 65535, ceil(C / 64) * G * Q < 2^31 blocks. */
+typedef struct {
+  const float* x; int64_t ld;
+  int64_t S; int64_t C;
+  const int32_t* group; const int32_t* ranks;
+  int32_t G; int32_t Q;
+  float* out;
+  int32_t* err_flag;
+} TecmColumnSelect;
+int tecm_column_select(const TecmColumnSelect* c, void* stream);
+
+/* (c) tecm_interval_stats: the intervals of the quantiles q_lo, q_hi (Gq, H, I) float32 contiguous -- q_lo NULL with
+ *     TECM_CONF_ABS, where q_lo = -q_hi; a sample of group g uses the quantiles of group g when Gq == G and those of group 0
+ *     when Gq == 1 -- per (sample, horizon, node), with r and w as above:
+ *       covered = (r <= q_hi) for ABS, (q_lo <= r <= q_hi) for SIGNED; a miss is `below` when y lies under the interval
+ *                 (ABS: y < p; SIGNED: r < q_lo) and `above` otherwise
+ *       lo = (float)(p + q_lo*w), hi = (float)(p + q_hi*w), evaluated in float64 from the float32 operands and rounded once,
+ *                 then both clamped to [clip_lo, clip_hi] when the clip is on
+ *       width = hi - lo,   Winkler score = width + (2/alpha) max(lo - y, 0) + (2/alpha) max(y - hi, 0), both in float64
+ *     ACCUMULATED across samples and calls into stats (G, H, 6, I) doubles, ((g*H + h)*6 + n)*I + i:
+ *       [count, covered, below, above, sum width, sum Winkler]
+ *     with the layout, ownership and order of (3b): one owning thread per cell adds the cell's samples in ascending s in
+ *     registers and then adds to `stats` once, no atomics; cells of a group that does not occur are neither read nor written;
+ *     an id outside [0, G) skips the sample everywhere (the per-sample outputs included) and sets TECM_BAD_GROUP.
+ *     Optional per-sample outputs (NULL skips one), float32 at out[s*o_stride_s + h*o_stride_h + i*o_stride_i]: out_lo, out_hi
+ *     and out_mid = p.  With target == NULL only these are written (stats may be NULL, alpha is not used): the forecast path.
+ *     Limits: G and ceil(H / 4) <= 65535, scale != 0, 0 < alpha < 1 with a target. */
+typedef struct {
+  const float* pred; int64_t p_stride_s, p_stride_h, p_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  const float* sigma; int64_t g_stride_s, g_stride_h, g_stride_i;
+  int64_t S; int32_t H; int32_t mode; int64_t I;
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  float sigma_min;
+  const float* q_lo; const float* q_hi;
+  int32_t Gq; int32_t G;
+  double alpha;
+  double* stats;
+  const int32_t* group;
+  int32_t* err_flag;
+  float* out_lo; float* out_hi; float* out_mid;
+  int64_t o_stride_s, o_stride_h, o_stride_i;
+} TecmIntervalStats;
+int tecm_interval_stats(const TecmIntervalStats* c, void* stream);
+
 /* (4) sliding-window batch assembly from device-resident series (SlidingWindowSamplerDataset.__getitem__
  * src/data/dataset.py:65-99 + the harness reshapes train.py:62-65, :76): for sample b with window
  * start a = starts[b] (already multiplied by the dataset stride):

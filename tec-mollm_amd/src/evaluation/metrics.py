@@ -9,6 +9,8 @@ from 8*L_out doubles in `compute()` -- the only device->host copy of the whole e
 `MapMetrics` keeps the same statistics per (group, horizon, node) cell instead of per horizon (`tecm_metrics_map`), and
 `derive` turns statistics of any leading shape into the metrics, NaN where a cell saw no sample.  `EnsembleMetrics` scores a
 K-member ensemble per cell the same way (`tecm_ensemble_stats`: CRPS, spread, coverage, rank histogram; `derive_ensemble`).
+`IntervalMetrics` scores conformal prediction intervals per cell (`tecm_interval_stats`: coverage, side of the misses, width,
+Winkler score; `derive_intervals`); the intervals themselves come from `tecmollm/conformal.py`.
 
 Same numbers as the reference: inverse StandardScaler transform, non-finite guards, clip of predictions
 to [0, 200] TECU, MAE / RMSE / R^2 (sklearn semantics) / Pearson r per horizon and their averages.
@@ -382,4 +384,119 @@ class EnsembleMetrics:
         out["rank_histogram"] = hs.sum(axis=2)
         out["by_group"] = [_pooled_ensemble(derive_ensemble(st[g].sum(axis=1), hs[g].sum(axis=1), self.K, self.trim))
                            for g in range(self.G)]
+        return out
+
+
+# ------------------------------------------------------------------------------------ conformal intervals
+INTERVAL_KEYS = ("count", "coverage", "miss_below", "miss_above", "interval_width", "interval_score")
+
+
+def derive_intervals(stats: np.ndarray) -> Dict[str, np.ndarray]:
+    """(..., 6) float64 sums [count, covered, below, above, sum width, sum Winkler] -> the INTERVAL_KEYS, arrays over the
+    leading axes, NaN where a cell saw no sample: coverage, miss_below and miss_above are the shares of the samples inside,
+    under and over their interval (they add up to 1), interval_width and interval_score (Winkler) the means."""
+    st = np.asarray(stats, dtype=np.float64)
+    if st.shape[-1] != _lib.TECM_INTERVAL_STATS:
+        raise ValueError(f"stats must be (..., {_lib.TECM_INTERVAL_STATS}), got {st.shape}")
+    n, cov, below, above, sw, ss = np.moveaxis(st, -1, 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = {"count": n.copy(), "coverage": cov / n, "miss_below": below / n, "miss_above": above / n,
+               "interval_width": sw / n, "interval_score": ss / n}
+    empty = n == 0
+    for k in INTERVAL_KEYS[1:]:
+        out[k] = np.where(empty, np.nan, out[k])
+    return out
+
+
+def _pooled_intervals(per: Dict[str, np.ndarray]) -> Dict[str, object]:
+    """`derive_intervals` of (H, ...) rows -> per key its list by horizon and the average over the horizons."""
+    out: Dict[str, object] = {"count_by_horizon": per["count"].tolist()}
+    for k in INTERVAL_KEYS[1:]:
+        out[f"{k}_by_horizon"] = per[k].tolist()
+        out[f"{k}_avg"] = float(np.mean(per[k]))
+    return out
+
+
+class IntervalMetrics:
+    """Coverage, the side of the misses, width and Winkler score of conformal intervals per cell (group of the sample,
+    horizon, node).  update(pred, true, q, groups) per batch on the device (one kernel, `tecm_interval_stats`: the score of
+    every sample is the one `ConformalCalibrator` stores, no atomics, so the same batches give the same bits), compute() at
+    the end.  It mirrors `EnsembleMetrics`."""
+
+    def __init__(self, num_horizons: int, num_nodes: int, num_groups: int = 1, scaler=None, alpha: float = 0.1,
+                 mode: str = "absolute", device: Union[str, torch.device] = "cuda", sigma_min: float = 1e-3):
+        from tecmollm import ops
+        self.H, self.I, self.G = int(num_horizons), int(num_nodes), int(num_groups)
+        if min(self.H, self.I, self.G) < 1:
+            raise ValueError("IntervalMetrics needs at least one horizon, one node and one group")
+        self.alpha = float(alpha)
+        if not 0.0 < self.alpha < 1.0:
+            raise ValueError(f"alpha must lie in (0, 1), got {alpha}")
+        if mode not in ops.CONFORMAL_MODES:
+            raise ValueError(f"mode must be one of {sorted(ops.CONFORMAL_MODES)}, got {mode!r}")
+        self.mode, self.sigma_min = mode, float(sigma_min)
+        self.scaler = _scaler_params(scaler)
+        # [g][h][k][i]: node-contiguous, the layout the kernel's lanes read and write
+        self.stats = torch.zeros(self.G, self.H, _lib.TECM_INTERVAL_STATS, self.I, device=device, dtype=torch.float64)
+
+    @property
+    def nominal_coverage(self) -> float:
+        return 1.0 - self.alpha
+
+    def reset(self) -> None:
+        self.stats.zero_()
+
+    def update(self, y_pred_scaled: torch.Tensor, y_true_scaled: Optional[torch.Tensor], q,
+               groups: Optional[torch.Tensor] = None, sigma: Optional[torch.Tensor] = None,
+               outputs=()) -> Dict[str, torch.Tensor]:
+        """pred and truth (S, H, N) or (S, H, N, 1) in scaled units, read in place whatever their strides; `q` = (q_lo, q_hi),
+        contiguous float32 device tensors (1 or G, H, N) with q_lo None in the absolute mode (`ConformalIntervals.on(device)`);
+        groups (S) int32 or None; sigma (S, H, N) in physical units or None.  With the truth None nothing is accumulated and
+        only the per-sample tensors are made.  Returns the tensors named in `outputs` (`ops.INTERVAL_OUTPUTS`), each (S, H, N)
+        float32 in physical units: lo, hi and mid, the centre of the interval."""
+        from tecmollm import devcheck, ops
+        p, S, H, I, ps, ph, pi = _as_shi(y_pred_scaled, "y_pred")
+        if H != self.H or I != self.I:
+            raise ValueError(f"shape mismatch: pred {tuple(y_pred_scaled.shape)}, horizons {self.H}, nodes {self.I}")
+        views = [p.as_strided((S, H, I), (ps, ph, pi))]
+        for t, name in ((y_true_scaled, "y_true"), (sigma, "sigma")):
+            if t is None:
+                views.append(None)
+                continue
+            t, S2, H2, I2, ts, th, ti = _as_shi(t, name)
+            if (S2, H2, I2) != (S, H, I):
+                raise ValueError(f"shape mismatch: pred {tuple(y_pred_scaled.shape)}, {name} {tuple(t.shape)}")
+            views.append(t.as_strided((S, H, I), (ts, th, ti)))
+        if groups is not None:
+            _lib.require_gpu_tensor(groups, "groups", torch.int32)
+            if groups.shape != (S,):
+                raise ValueError(f"groups must hold one id per sample: {tuple(groups.shape)} for {S} samples")
+            groups = groups.contiguous()
+        q_lo, q_hi = q
+        mean, scale = self.scaler if self.scaler is not None else (0.0, 1.0)
+        errs = devcheck.error_word(self.stats.device)
+        outs = {name: torch.empty(S, H, I, device=p.device, dtype=torch.float32) for name in outputs}
+        ops.interval_stats(views[0], views[1], q_lo, q_hi, self.stats, alpha=self.alpha, mode=self.mode, sigma=views[2],
+                           sigma_min=self.sigma_min, mean=mean, scale=scale,
+                           clip=(TEC_MIN, TEC_MAX) if self.scaler is not None else None, groups=groups,
+                           err_flag=errs.ptr(), outputs=outs)
+        if groups is not None:
+            errs.post()                        # only a group id can set the word here
+        return outs
+
+    def merge_(self, group=None) -> "IntervalMetrics":
+        """Sum the statistics over the ranks of `group` with one all-reduce, in place (see `HorizonMetrics.merge_`)."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            dist.all_reduce(self.stats, op=dist.ReduceOp.SUM, group=group)
+        return self
+
+    def compute(self) -> Dict[str, object]:
+        """The INTERVAL_KEYS as numpy (G, H, N) arrays, NaN where a cell saw no sample; "nominal_coverage" = 1 - alpha;
+        "by_group": per group the scores of its statistics pooled over the nodes, by horizon and averaged over the horizons
+        (NaN for a group never visited)."""
+        st = self.stats.permute(0, 1, 3, 2).cpu().numpy()                   # (G, H, I, 6)
+        out: Dict[str, object] = dict(derive_intervals(st))
+        out["nominal_coverage"] = self.nominal_coverage
+        out["by_group"] = [_pooled_intervals(derive_intervals(st[g].sum(axis=1))) for g in range(self.G)]
         return out

@@ -3,7 +3,8 @@
 Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
   csrc/            hand-written HIP kernels + the C ABI (include/tecmollm.h at the repo root)
   tecmollm/        ctypes binding, autograd stage functions, graph preparation, training-step helpers, test-split evaluation,
-                   input attribution, ensemble forecasts and their scores, spatial attention maps
+                   input attribution, ensemble forecasts and their scores, spatial attention maps, conformal
+                   prediction intervals
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/models/      mirror of the reference's baselines (`from src.models.baselines import HistoricalAverage`)
 """
@@ -14,6 +15,9 @@ from .functions import dropout_seed  # noqa: F401
 from . import ensemble  # noqa: F401
 from .ensemble import (ensemble_forecast, ensemble_members, evaluate_ensemble, member_seed,  # noqa: F401
                        write_ensemble)
+from . import conformal  # noqa: F401
+from .conformal import (ConformalCalibrator, ConformalIntervals, calibrate_conformal, conformal_forecast,  # noqa: F401
+                        conformal_ranks, evaluate_conformal, write_conformal)
 from .spatial_attention import (AttentionStats, attention_maps, evaluate_attention, graph_groups_by_lag,  # noqa: F401
                                 graph_groups_by_sample, graph_groups_by_slot, spatial_attention, write_attention)
 
@@ -21,4 +25,5 @@ __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradien
            "attribution_maps", "write_attributions", "dropout_seed", "ensemble", "member_seed", "ensemble_members",
            "ensemble_forecast", "evaluate_ensemble", "write_ensemble", "spatial_attention", "AttentionStats",
            "evaluate_attention", "attention_maps", "write_attention", "graph_groups_by_sample", "graph_groups_by_slot",
-           "graph_groups_by_lag"]
+           "graph_groups_by_lag", "conformal", "conformal_ranks", "ConformalCalibrator", "ConformalIntervals",
+           "calibrate_conformal", "conformal_forecast", "evaluate_conformal", "write_conformal"]

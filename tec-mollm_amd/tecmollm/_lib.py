@@ -149,6 +149,42 @@ class TecmEnsemble(C.Structure):
     ]
 
 
+class TecmConformalScores(C.Structure):
+    _fields_ = [
+        ("pred", c_f32p), ("p_stride_s", C.c_int64), ("p_stride_h", C.c_int64), ("p_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("sigma", c_f32p), ("g_stride_s", C.c_int64), ("g_stride_h", C.c_int64), ("g_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("mode", C.c_int32), ("I", C.c_int64),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("sigma_min", C.c_float),
+        ("scores", c_f32p), ("ld", C.c_int64), ("row0", C.c_int64),
+    ]
+
+
+class TecmColumnSelect(C.Structure):
+    _fields_ = [
+        ("x", c_f32p), ("ld", C.c_int64), ("S", C.c_int64), ("C", C.c_int64),
+        ("group", C.c_void_p), ("ranks", C.c_void_p), ("G", C.c_int32), ("Q", C.c_int32),
+        ("out", c_f32p), ("err_flag", C.c_void_p),
+    ]
+
+
+class TecmIntervalStats(C.Structure):
+    _fields_ = [
+        ("pred", c_f32p), ("p_stride_s", C.c_int64), ("p_stride_h", C.c_int64), ("p_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("sigma", c_f32p), ("g_stride_s", C.c_int64), ("g_stride_h", C.c_int64), ("g_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("mode", C.c_int32), ("I", C.c_int64),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("sigma_min", C.c_float),
+        ("q_lo", c_f32p), ("q_hi", c_f32p), ("Gq", C.c_int32), ("G", C.c_int32),
+        ("alpha", C.c_double),
+        ("stats", C.c_void_p), ("group", C.c_void_p), ("err_flag", C.c_void_p),
+        ("out_lo", c_f32p), ("out_hi", c_f32p), ("out_mid", c_f32p),
+        ("o_stride_s", C.c_int64), ("o_stride_h", C.c_int64), ("o_stride_i", C.c_int64),
+    ]
+
+
 class TecmWindowBatch(C.Structure):
     _fields_ = [
         ("X", c_f32p), ("TF", c_f32p), ("Y", c_f32p), ("starts", C.c_void_p), ("starts_host_check", C.c_void_p),
@@ -223,6 +259,9 @@ TECM_METRIC_STATS = 8
 TECM_MAP_LDS_MAX_H = 32
 TECM_ENS_STATS = 9
 TECM_ENS_MAX_K = 64
+TECM_CONF_ABS, TECM_CONF_SIGNED = 0, 1
+TECM_INTERVAL_STATS = 6
+TECM_SELECT_MAX_Q = 8
 TECM_ATTN_SKIP_UNCONNECTED = 1
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
 TECM_SAR_MAX_K, TECM_SAR_MAX_LAG, TECM_SAR_MAX_LONG_AR, TECM_SAR_MAX_OFFSET, TECM_SAR_CHUNK = 12, 32, 64, 64, 1024
@@ -321,6 +360,9 @@ EXPORTS = {
     "tecm_metrics_accumulate": (C.c_int, [C.POINTER(TecmMetrics), C.c_void_p]),
     "tecm_metrics_map": (C.c_int, [C.POINTER(TecmMetricsMap), C.c_void_p]),
     "tecm_ensemble_stats": (C.c_int, [C.POINTER(TecmEnsemble), C.c_void_p]),
+    "tecm_conformal_scores": (C.c_int, [C.POINTER(TecmConformalScores), C.c_void_p]),
+    "tecm_column_select": (C.c_int, [C.POINTER(TecmColumnSelect), C.c_void_p]),
+    "tecm_interval_stats": (C.c_int, [C.POINTER(TecmIntervalStats), C.c_void_p]),
     "tecm_window_batch": (C.c_int, [C.POINTER(TecmWindowBatch), C.c_void_p]),
     "tecm_window_baseline": (C.c_int, [C.POINTER(TecmWindowBaseline), C.c_void_p]),
     "tecm_slot_mean": (C.c_int, [C.POINTER(TecmSlotMean), C.c_void_p]),

@@ -113,16 +113,19 @@ def get_baseline_predictions(test_dataset, L_in: int, L_out: int) -> np.ndarray:
     return out.cpu().numpy()
 
 
-def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_weight, order, groups, num_groups):
-    """The one pass over the batches that `evaluate_split` and `evaluate_maps` share: every forecast feeds a `HorizonMetrics`
-    of its own and, when `num_groups` is given, a `MapMetrics` too.  Returns ({name: HorizonMetrics}, {name: MapMetrics})."""
+def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_weight, order, groups, num_groups,
+                per_batch=None):
+    """The one pass over the batches that `evaluate_split`, `evaluate_maps` and `evaluate_conformal` share: every forecast
+    feeds a `HorizonMetrics` of its own and, when `num_groups` is given, a `MapMetrics` too.  `per_batch(ordinal, x, tf, y,
+    out, ids)`, when given, sees every batch after its forecasts are scored.
+    Returns ({name: HorizonMetrics}, {name: MapMetrics})."""
     from src.evaluation.metrics import HorizonMetrics, MapMetrics
     kinds = list(baselines)
     names = [baseline_name(k) for k in kinds]
     model.eval()
     hms: Dict[str, HorizonMetrics] = {}
     mms: Dict[str, MapMetrics] = {}
-    for chunk in _batches(len(dataset), batch_size, order):
+    for ordinal, chunk in enumerate(_batches(len(dataset), batch_size, order)):
         x, tf, y = dataset.batch(chunk)
         out = model(x, tf, edge_index, edge_weight)
         if not hms:
@@ -138,6 +141,8 @@ def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_
             hms[name].update(pred, y)
             if mms:
                 mms[name].update(pred, y, ids)
+        if per_batch is not None:
+            per_batch(ordinal, x, tf, y, out, ids)
     return hms, mms
 
 

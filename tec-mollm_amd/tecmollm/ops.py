@@ -775,6 +775,132 @@ def ensemble_stats(members: torch.Tensor, target: torch.Tensor, stats: torch.Ten
     check(lib().tecm_ensemble_stats(C.byref(e), stream_ptr()), "tecm_ensemble_stats")
 
 
+CONFORMAL_MODES = {"absolute": _lib.TECM_CONF_ABS, "signed": _lib.TECM_CONF_SIGNED}
+INTERVAL_OUTPUTS = ("lo", "hi", "mid")
+
+
+def _conformal_mode(mode) -> int:
+    if mode not in CONFORMAL_MODES:
+        raise ValueError(f"mode must be one of {sorted(CONFORMAL_MODES)}, got {mode!r}")
+    return CONFORMAL_MODES[mode]
+
+
+def _shi(t: Optional[torch.Tensor], shape, name: str):
+    """(pointer, stride_s, stride_h, stride_i) of an (S, H, I) float32 device view; (None, 0, 0, 0) for None."""
+    if t is None:
+        return None, 0, 0, 0
+    _lib.require_gpu_tensor(t, name)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must be (S, H, I) = {tuple(shape)}, got {tuple(t.shape)}")
+    return t.data_ptr(), t.stride(0), t.stride(1), t.stride(2)
+
+
+def conformal_scores(pred: torch.Tensor, target: torch.Tensor, scores: torch.Tensor, row0: int = 0, *,
+                     mode: str = "absolute", sigma: Optional[torch.Tensor] = None, sigma_min: float = 1e-3,
+                     mean: float = 0.0, scale: float = 1.0, clip: Optional[Tuple[float, float]] = None) -> None:
+    """tecm_conformal_scores (include/tecmollm.h (3g)(a)): the scores of `pred` against `target`, (S, H, I) float32 views of
+    any strides read in place, into rows row0 .. row0 + S - 1 of the 2-D float32 store `scores` (rows of H*I values, leading
+    dimension scores.stride(0)).  `sigma` (S, H, I) in physical units divides the score by max(sigma, sigma_min)."""
+    S, H, I = pred.shape
+    pp, ps, ph, pi = _shi(pred, (S, H, I), "pred")
+    tp, ts, th, ti = _shi(target, (S, H, I), "target")
+    gp, gs, gh, gi = _shi(sigma, (S, H, I), "sigma")
+    _lib.require_gpu_tensor(scores, "scores")
+    if scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[1] < H * I or not 0 <= row0 <= scores.shape[0] - S:
+        raise ValueError(f"scores must be a row-major (rows >= {row0 + S}, columns >= {H * I}) store, got {tuple(scores.shape)}")
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    c = _lib.TecmConformalScores(pred=pp, p_stride_s=ps, p_stride_h=ph, p_stride_i=pi, target=tp, t_stride_s=ts,
+                                 t_stride_h=th, t_stride_i=ti, sigma=gp, g_stride_s=gs, g_stride_h=gh, g_stride_i=gi,
+                                 S=S, H=H, mode=_conformal_mode(mode), I=I, mean=float(mean), scale=float(scale),
+                                 clip_lo=lo, clip_hi=hi, clip=1 if clip is not None else 0, sigma_min=float(sigma_min),
+                                 scores=scores.data_ptr(), ld=scores.stride(0), row0=int(row0))
+    check(lib().tecm_conformal_scores(C.byref(c), stream_ptr()), "tecm_conformal_scores")
+
+
+def column_select(x: torch.Tensor, ranks: torch.Tensor, groups: Optional[torch.Tensor] = None, err_flag: int = 0,
+                  columns: Optional[int] = None) -> torch.Tensor:
+    """tecm_column_select (include/tecmollm.h (3g)(b)): the ranks[g, q]-th smallest (1-based) of every column of the rows of
+    group g of `x`, a 2-D float32 device tensor with contiguous rows (any leading dimension; `columns` limits the search to
+    the first so many columns).  `ranks` (G, Q) int32 on the device, `groups` (S) int32 on the device or None (one group),
+    `err_flag` the address of the device error word (tecmollm/devcheck.py).  Returns (Q, G, C) float32: -inf for a rank
+    <= 0, +inf for a rank above the group's row count, numpy's sort order otherwise (NaN last)."""
+    _lib.require_gpu_tensor(x, "x")
+    _lib.require_gpu_tensor(ranks, "ranks", torch.int32)
+    if x.dim() != 2 or x.stride(1) != 1 and x.shape[1] > 1:
+        raise ValueError("x must be a 2-D tensor with contiguous rows")
+    S, Cn = x.shape[0], int(x.shape[1] if columns is None else columns)
+    if ranks.dim() != 2 or not ranks.is_contiguous():
+        raise ValueError("ranks must be a contiguous (G, Q) tensor")
+    if not 0 < Cn <= x.shape[1]:
+        raise ValueError(f"columns must lie in (0, {x.shape[1]}], got {Cn}")
+    G, Q = ranks.shape
+    if groups is not None:
+        _lib.require_gpu_tensor(groups, "groups", torch.int32)
+        if groups.shape != (S,) or not groups.is_contiguous():
+            raise ValueError(f"groups must hold one contiguous id per row: {tuple(groups.shape)} for {S} rows")
+    out = torch.empty(Q, G, Cn, device=x.device, dtype=torch.float32)
+    c = _lib.TecmColumnSelect(x=x.data_ptr(), ld=x.stride(0) if S > 1 else max(x.stride(0), Cn), S=S, C=Cn, group=ptr(groups),
+                              ranks=ranks.data_ptr(), G=G, Q=Q, out=out.data_ptr(), err_flag=err_flag or None)
+    check(lib().tecm_column_select(C.byref(c), stream_ptr()), "tecm_column_select")
+    return out
+
+
+def interval_stats(pred: torch.Tensor, target: Optional[torch.Tensor], q_lo: Optional[torch.Tensor], q_hi: torch.Tensor,
+                   stats: Optional[torch.Tensor], *, alpha: float = 0.1, mode: str = "absolute",
+                   sigma: Optional[torch.Tensor] = None, sigma_min: float = 1e-3, mean: float = 0.0, scale: float = 1.0,
+                   clip: Optional[Tuple[float, float]] = None, groups: Optional[torch.Tensor] = None, num_groups: int = 1,
+                   err_flag: int = 0, outputs: Optional[dict] = None) -> None:
+    """tecm_interval_stats (include/tecmollm.h (3g)(c)): one update of `stats` (G, H, 6, I) float64 from `pred`, `target`
+    (S, H, I) float32 views read in place and the quantiles `q_lo` (None in the absolute mode), `q_hi`, contiguous (Gq, H, I)
+    float32 with Gq = 1 or G.  `outputs` maps names of INTERVAL_OUTPUTS to (S, H, I) float32 tensors that share their strides.
+    With `target` None only the outputs are written and `stats` may be None (G = `num_groups`)."""
+    S, H, I = pred.shape
+    pp, ps, ph, pi = _shi(pred, (S, H, I), "pred")
+    tp, ts, th, ti = _shi(target, (S, H, I), "target")
+    gp, gs, gh, gi = _shi(sigma, (S, H, I), "sigma")
+    G = int(num_groups) if stats is None else stats.shape[0]
+    if stats is not None and (stats.shape != (G, H, _lib.TECM_INTERVAL_STATS, I) or stats.dtype != torch.float64
+                              or not stats.is_contiguous()):
+        raise ValueError(f"stats must be a contiguous float64 (G, {H}, {_lib.TECM_INTERVAL_STATS}, {I}) tensor")
+    m = _conformal_mode(mode)
+    Gq = q_hi.shape[0]
+    for name, t in (("q_lo", q_lo), ("q_hi", q_hi)):
+        if t is None:
+            continue
+        _lib.require_gpu_tensor(t, name)
+        if t.shape != (Gq, H, I) or not t.is_contiguous() or Gq not in (1, G):
+            raise ValueError(f"{name} must be a contiguous (1 or {G}, {H}, {I}) tensor, got {tuple(t.shape)}")
+    if (q_lo is None) != (m == _lib.TECM_CONF_ABS):
+        raise ValueError("q_lo is given in the signed mode and only there")
+    if groups is not None:
+        _lib.require_gpu_tensor(groups, "groups", torch.int32)
+        if groups.shape != (S,) or not groups.is_contiguous():
+            raise ValueError(f"groups must hold one contiguous id per sample: {tuple(groups.shape)} for {S} samples")
+    outs = dict(outputs or {})
+    unknown = set(outs) - set(INTERVAL_OUTPUTS)
+    if unknown:
+        raise ValueError(f"outputs must come from {INTERVAL_OUTPUTS}, got {sorted(unknown)}")
+    o_strides = (0, 0, 0)
+    for name, t in outs.items():
+        _lib.require_gpu_tensor(t, name)
+        if t.shape != (S, H, I):
+            raise ValueError(f"output {name} must be (S, H, I) = {(S, H, I)}, got {tuple(t.shape)}")
+        if o_strides == (0, 0, 0):
+            o_strides = tuple(t.stride())
+        elif tuple(t.stride()) != o_strides:
+            raise ValueError("the per-sample outputs must share their strides")
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    c = _lib.TecmIntervalStats(pred=pp, p_stride_s=ps, p_stride_h=ph, p_stride_i=pi, target=tp, t_stride_s=ts, t_stride_h=th,
+                               t_stride_i=ti, sigma=gp, g_stride_s=gs, g_stride_h=gh, g_stride_i=gi, S=S, H=H, mode=m, I=I,
+                               mean=float(mean), scale=float(scale), clip_lo=lo, clip_hi=hi,
+                               clip=1 if clip is not None else 0, sigma_min=float(sigma_min), q_lo=ptr(q_lo),
+                               q_hi=q_hi.data_ptr(), Gq=Gq, G=G, alpha=float(alpha), stats=ptr(stats), group=ptr(groups),
+                               err_flag=err_flag or None, out_lo=ptr(outs.get("lo")), out_hi=ptr(outs.get("hi")),
+                               out_mid=ptr(outs.get("mid")), o_stride_s=o_strides[0], o_stride_h=o_strides[1],
+                               o_stride_i=o_strides[2])
+    check(lib().tecm_interval_stats(C.byref(c), stream_ptr()), "tecm_interval_stats")
+
+
 def spatial_attention_ws_floats(d: "_lib.TecmSpatial", num_edges: int, accumulate: bool) -> int:
     """tecm_spatial_attention_ws_floats: floats of workspace the call asks for by default (one chunk of graphs, at most
     64 MiB unless one graph needs more), 0 when the descriptor is not served.  Pure host arithmetic."""

@@ -455,6 +455,63 @@ int tecm_attention_bwd(const float* qkv, const float* dctx, void* dqkv, int32_t 
  * zero-rectangle hint) -- and 1 for every other T the entry points accept.  Pure host function. */
 int tecm_attention_reads_q0(int32_t T);
 
+/* The causal attention probabilities of one GPT-2 block, handed to the caller (csrc/attention_probs.hip): what Hugging Face's
+ * GPT2Attention returns for output_attentions=True (modeling_gpt2.py:144-226) at the reference's call site
+ * (LLMBackbone.forward, modules.py:205-209), BEFORE the attention dropout -- what eval() uses and what training draws its
+ * masks over.  The production kernels (tecm_attention_fwd) form them in registers and keep only ctx.
+ *   p_ij = exp(s_ij - max_j s_ij) / sum_{j<=i} exp(s_ij - max),   s_ij = (q_i . k_j) / 8,   all fp32;
+ * the denominator is the fp32 sum of exactly the i + 1 numerators that are then divided (no online rescaling), so a row sums
+ * to 1 within (i + 2) * 2^-24.  Row 0 is [1, 0, ...] by definition: the q columns of the token-0 rows are NEVER read, at any
+ * T (in fp32 mode the c_attn GEMM leaves them unwritten for the T of tecm_attention_reads_q0).
+ * qkv: one layer's (B,T,N,3*D) buffer exactly as tecm_attention_fwd reads it (time-major rows (b*T + p)*N + n, columns
+ * [q | k | v], head h at columns h*64..); fp32, or bf16 with TECM_ATT_QKV_BF16 in `flags`.  Only q and k are read.
+ * D / heads must be 64 and 1 <= T <= 1024.  T <= 32: 16 lanes per (sequence, head), the keys register-resident; 33 <= T:
+ * a wave per (sequence, head), q_i in registers, the keys split over the lanes, the row's scores parked in LDS.
+ *   raw export    probs (B, Ns, heads, T, T) floats; entries j > i are written as exact +0.  nodes (Ns) int32 on the device
+ *                 names the nodes exported (NULL: all N in order, Ns = N); an id outside [0, N) leaves its slot all zero.
+ *   accumulation  for layer slot `layer` of `num_layers` and the group g of every window b (group (B) int32 on the device,
+ *                 NULL: group 0), every quantity formed in float64 from the fp32 p that is (or would be) exported, the
+ *                 logarithm included, 0 ln 0 = 0:
+ *                   node_stats (G, Ly, 4, N, heads): sums over the group's windows of, per sequence (b, n) and head,
+ *                       [entropy (1/T) sum_i -sum_j p_ij ln p_ij, look-back (1/T) sum_i sum_j p_ij (i - j), sink (1/T) sum_i p_i0,
+ *                        self (1/T) sum_i p_ii]
+ *                   lag_stats (G, Ly, heads, T):  L_d = sum over sequences of sum_{i>=d} p_{i,i-d}
+ *                   matrix_stats (G, Ly, heads, T, T) or NULL: sum of p_ij over sequences; T <= 32 only
+ *                   counts (G) int64: windows added, advanced only with TECM_TATT_COUNT in `flags` (one layer of an update
+ *                       counts, not every layer)
+ *                 An id outside [0, num_groups) skips the window in every sum and sets TECM_BAD_GROUP in *err_flag, never
+ *                 clamped.  No floating-point atomics: the sums over the nodes of a window go through per-block partial sums
+ *                 whose tree is fixed by (N, T) alone, and every cell has ONE owning thread that adds the windows of the call in
+ *                 ascending b with plain loads and stores -- the same calls in the same order give the same bits, whatever the
+ *                 workspace size.
+ * Either part may be left out (probs NULL / node_stats NULL), not both.  With node_stats: lag_stats, counts, err_flag and
+ * num_groups, num_layers > 0 are required.
+ * ws: the accumulation walks chunks of whole windows through it (4 doubles per (sequence, head), and per block of 16 (T <= 32)
+ * or 4 (T > 32) nodes and head T (+ T*T with matrix_stats) doubles); 16-byte aligned.  ws_floats = floats it holds, 0 =
+ * tecm_temporal_attention_ws_floats(a), which is at most 64 MiB unless one window needs more; any size that holds one window
+ * is accepted (smaller: more chunks, same bits).  The export alone uses no workspace (ws may be NULL). */
+#define TECM_TATT_COUNT 8                 /* flags: this call advances counts (next to TECM_ATT_QKV_BF16) */
+typedef struct TecmTemporalAttn {
+  const void* qkv;                        /* (B,T,N,3*D) fp32 or bf16 */
+  float* probs;                           /* (B, Ns, heads, T, T) or NULL */
+  const int32_t* nodes;                   /* (Ns) or NULL = all N */
+  double* node_stats;                     /* (G, Ly, 4, N, heads) or NULL = no accumulation */
+  double* lag_stats;                      /* (G, Ly, heads, T) */
+  double* matrix_stats;                   /* (G, Ly, heads, T, T) or NULL */
+  int64_t* counts;                        /* (G) */
+  const int32_t* group;                   /* (B) or NULL */
+  int32_t* err_flag;                      /* the device error word (TecmSpatial::err_flag) */
+  float* ws; int64_t ws_floats;           /* 16-byte aligned; contents undefined after */
+  int32_t B, T, N, heads, D;
+  int32_t Ns;                             /* entries of `nodes`; ignored (N) when nodes is NULL */
+  int32_t num_groups, num_layers, layer;  /* G, Ly, the layer slot this call adds to */
+  int32_t flags;                          /* TECM_ATT_QKV_BF16 | TECM_TATT_COUNT */
+} TecmTemporalAttn;
+/* Floats of workspace the call asks for by default (4 when only the export is asked for, which needs none), or 0 when `a` is
+ * not served.  Pure host function. */
+int64_t tecm_temporal_attention_ws_floats(const TecmTemporalAttn* a);
+int tecm_temporal_attention(const TecmTemporalAttn* a, void* stream);
+
 /* ------------------------------------------------------------------ reductions / small ops
  * out[s][c] (+)= sum over rows r = o*outer_stride + j (o < outer, j < inner) + seg s offset
  * of in[r*ld + c]; row(s,o,j) = (o*nseg + s)*inner + j when nseg > 1 (wpe / bias gradients). */

@@ -61,7 +61,8 @@ def make_plan(module: nn.Module, p: float = 0.1, precision: str = "auto") -> F_.
     base = F_.pinned_dropout_seed()
     if base is None:
         base = torch.initial_seed() + 7919 * _seed_counter[0]
-    return F_.DropPlan(training=module.training, p=p, base_seed=base, bf16=bf16)
+    tap = F_.active_attention_tap()             # inside `F_.attention_tap`: the eval-mode forward, with the tap on its blocks
+    return F_.DropPlan(training=module.training and tap is None, p=p, base_seed=base, bf16=bf16, attn_tap=tap)
 
 
 def _need_cuda(t: torch.Tensor, name: str):
@@ -358,9 +359,14 @@ class LLMBackbone(nn.Module):
         """h0 (B, T, N, 768) = inputs_embeds + wpe (already added by the patch GEMM epilogue)."""
         return F_.GPT2StackFn.apply(h0, self.num_layers, plan, *self.stack_params())
 
-    def forward(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def forward(self, inputs_embeds: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
+                output_attentions: bool = False):
         """Reference signature (modules.py:205-209): (S, T, 768) -> last_hidden_state (S, T, 768).
-        attention_mask must be all ones (tec_mollm.py:111) -- the kernel is purely causal."""
+        attention_mask must be all ones (tec_mollm.py:111) -- the kernel is purely causal.
+        `output_attentions` truthy (Hugging Face's keyword, modeling_gpt2.py:144-226): returns (last_hidden_state,
+        attentions) with attentions a tuple of `num_layers` detached (S, 12, T, T) float32 tensors, the causal softmax of every
+        block BEFORE the attention dropout (in training mode Hugging Face hands out the dropped weights; these are the
+        ones the masks are drawn over).  last_hidden_state is the same, bit for bit, with and without the keyword."""
         _need_cuda(inputs_embeds, "inputs_embeds")
         S, T, D = inputs_embeds.shape
         plan = make_plan(self)
@@ -376,8 +382,18 @@ class LLMBackbone(nn.Module):
         h0 = inputs_embeds + wpe[:T]                     # stand-alone use only; fused path adds wpe in the GEMM
         if plan.training and plan.p > 0:
             h0 = torch.nn.functional.dropout(h0, plan.p, True)
-        out = self.forward_tm(h0.contiguous().view(S, T, 1, D), plan)
-        return out.view(S, T, D)
+        if not output_attentions:
+            out = self.forward_tm(h0.contiguous().view(S, T, 1, D), plan)
+            return out.view(S, T, D)
+        attentions: List[Optional[torch.Tensor]] = [None] * self.num_layers
+
+        def tap(layer, qkv, B_, T_, N_):
+            probs = torch.empty(B_, N_, F_.GPT_HEADS, T_, T_, device=qkv.device, dtype=torch.float32)
+            F_.ops.temporal_attention(qkv.detach(), B_, T_, N_, F_.GPT_HEADS, D, probs=probs)
+            attentions[layer] = probs.view(B_ * N_, F_.GPT_HEADS, T_, T_)
+
+        out = self.forward_tm(h0.contiguous().view(S, T, 1, D), dataclasses.replace(plan, attn_tap=tap))
+        return out.view(S, T, D), tuple(attentions)
 
 
 class SpatioTemporalEmbedding(nn.Module):

@@ -3,7 +3,7 @@
 Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
   csrc/            hand-written HIP kernels + the C ABI (include/tecmollm.h at the repo root)
   tecmollm/        ctypes binding, autograd stage functions, graph preparation, training-step helpers, test-split evaluation,
-                   input attribution, ensemble forecasts and their scores, spatial attention maps, conformal
+                   input attribution, ensemble forecasts and their scores, spatial and temporal attention maps, conformal
                    prediction intervals
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/models/      mirror of the reference's baselines (`from src.models.baselines import HistoricalAverage`)
@@ -20,10 +20,13 @@ from .conformal import (ConformalCalibrator, ConformalIntervals, calibrate_confo
                         conformal_ranks, evaluate_conformal, write_conformal)
 from .spatial_attention import (AttentionStats, attention_maps, evaluate_attention, graph_groups_by_lag,  # noqa: F401
                                 graph_groups_by_sample, graph_groups_by_slot, spatial_attention, write_attention)
+from .temporal_attention import (TemporalAttentionStats, evaluate_temporal_attention, temporal_attention,  # noqa: F401
+                                 write_temporal_attention)
 
 __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradient", "integrated_gradients",
            "attribution_maps", "write_attributions", "dropout_seed", "ensemble", "member_seed", "ensemble_members",
            "ensemble_forecast", "evaluate_ensemble", "write_ensemble", "spatial_attention", "AttentionStats",
            "evaluate_attention", "attention_maps", "write_attention", "graph_groups_by_sample", "graph_groups_by_slot",
            "graph_groups_by_lag", "conformal", "conformal_ranks", "ConformalCalibrator", "ConformalIntervals",
-           "calibrate_conformal", "conformal_forecast", "evaluate_conformal", "write_conformal"]
+           "calibrate_conformal", "conformal_forecast", "evaluate_conformal", "write_conformal", "temporal_attention",
+           "TemporalAttentionStats", "evaluate_temporal_attention", "write_temporal_attention"]

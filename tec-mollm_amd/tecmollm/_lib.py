@@ -93,6 +93,16 @@ class TecmSpatialAttn(C.Structure):
     ]
 
 
+class TecmTemporalAttn(C.Structure):
+    _fields_ = [
+        ("qkv", C.c_void_p), ("probs", c_f32p), ("nodes", C.c_void_p), ("node_stats", C.c_void_p),
+        ("lag_stats", C.c_void_p), ("matrix_stats", C.c_void_p), ("counts", C.c_void_p), ("group", C.c_void_p),
+        ("err_flag", C.c_void_p), ("ws", c_f32p), ("ws_floats", C.c_int64),
+        ("B", C.c_int32), ("T", C.c_int32), ("N", C.c_int32), ("heads", C.c_int32), ("D", C.c_int32), ("Ns", C.c_int32),
+        ("num_groups", C.c_int32), ("num_layers", C.c_int32), ("layer", C.c_int32), ("flags", C.c_int32),
+    ]
+
+
 class TecmLnAdd(C.Structure):
     _fields_ = [("dy2", C.c_void_p), ("ld", C.c_int64), ("bf16", C.c_int32), ("_pad", C.c_int32), ("drop", TecmDrop)]
 
@@ -263,6 +273,7 @@ TECM_CONF_ABS, TECM_CONF_SIGNED = 0, 1
 TECM_INTERVAL_STATS = 6
 TECM_SELECT_MAX_Q = 8
 TECM_ATTN_SKIP_UNCONNECTED = 1
+TECM_TATT_COUNT = 8
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
 TECM_SAR_MAX_K, TECM_SAR_MAX_LAG, TECM_SAR_MAX_LONG_AR, TECM_SAR_MAX_OFFSET, TECM_SAR_CHUNK = 12, 32, 64, 64, 1024
 TECM_SAR_DEGENERATE, TECM_SAR_NONFINITE, TECM_SAR_MA_DROPPED = 1, 2, 4
@@ -293,6 +304,8 @@ EXPORTS = {
     "tecm_spatial_dx": (C.c_int, [C.POINTER(TecmSpatial), C.POINTER(TecmSpatialDx), C.c_void_p]),
     "tecm_spatial_attention_ws_floats": (C.c_int64, [C.POINTER(TecmSpatial), C.POINTER(TecmSpatialAttn)]),
     "tecm_spatial_attention": (C.c_int, [C.POINTER(TecmSpatial), C.POINTER(TecmSpatialAttn), C.c_void_p]),
+    "tecm_temporal_attention_ws_floats": (C.c_int64, [C.POINTER(TecmTemporalAttn)]),
+    "tecm_temporal_attention": (C.c_int, [C.POINTER(TecmTemporalAttn), C.c_void_p]),
     "tecm_groupnorm_gelu_fwd": (C.c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int32, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_float, C.c_int32, C.c_int32, C.c_void_p]),
     "tecm_gn_y16_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32]),

@@ -13,7 +13,7 @@ import contextlib
 import os
 from dataclasses import dataclass
 import weakref
-from typing import List, Optional
+from typing import Callable, List, Optional
 
 import torch
 
@@ -88,6 +88,9 @@ class DropPlan:
     # blocks keep their input h only and re-run their forward in the backward; 2 = 1 + the conv blocks keep their input only
     recompute: int = 0
     keep: bool = True        # False: no backward will run (grad mode off, or nothing requires grad): keep nothing across layers
+    # optional tap on the GPT-2 blocks: called as attn_tap(layer, qkv, B, T, N) right after the block's attention launch is
+    # queued and before qkv is dropped (tecmollm/temporal_attention.py reads the attention probabilities from it)
+    attn_tap: Optional[Callable] = None
 
     def spec(self, site: int, ld: int):
         if not self.training or self.p <= 0.0:
@@ -111,6 +114,27 @@ def dropout_seed(base_seed: int):
         yield
     finally:
         _seed_override[0] = prev
+
+
+_attn_tap: List[Optional[Callable]] = [None]           # the tap of every plan made inside `attention_tap`, None outside
+
+
+@contextlib.contextmanager
+def attention_tap(tap: Callable):
+    """Every forward called inside this context runs as the eval-mode forward (no dropout at any site, whatever the module's
+    training flag says, which is left alone) and hands each GPT-2 block's qkv to `tap(layer, qkv, B, T, N)`
+    (`DropPlan.attn_tap`)."""
+    prev = _attn_tap[0]
+    _attn_tap[0] = tap
+    try:
+        yield
+    finally:
+        _attn_tap[0] = prev
+
+
+def active_attention_tap() -> Optional[Callable]:
+    """The tap of the innermost active `attention_tap` context, None outside."""
+    return _attn_tap[0]
 
 
 def pinned_dropout_seed() -> Optional[int]:
@@ -884,6 +908,8 @@ class GPT2StackFn(torch.autograd.Function):
         cx = torch.empty(M, D, device=h.device, dtype=torch.bfloat16 if a16 else torch.float32)
         aspec = plan.spec(site_attn(i), 1)
         ops.attention_fwd(qkv, cx, B, T, N, GPT_HEADS, D, aspec)
+        if plan.attn_tap is not None and out:               # (out False: the backward's recompute of a block already tapped)
+            plan.attn_tap(i, qkv, B, T, N)
         if not keep:
             qkv = None
         h2 = _empty(M, D, like=h)

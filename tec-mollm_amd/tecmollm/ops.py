@@ -443,6 +443,76 @@ def attention_reads_q0(T: int) -> bool:
     return bool(lib().tecm_attention_reads_q0(T))
 
 
+def temporal_attention_ws_floats(B: int, T: int, N: int, heads: int, D: int, accumulate: bool, matrix: bool = False) -> int:
+    """tecm_temporal_attention_ws_floats: floats of workspace the call asks for by default (one chunk of whole windows, at
+    most 64 MiB unless one window needs more; 4 for the export alone, which uses none), 0 when the shape is not served.
+    Pure host arithmetic."""
+    a = _lib.TecmTemporalAttn(B=B, T=T, N=N, heads=heads, D=D, probs=None if accumulate else 8,
+                              node_stats=8 if accumulate else None,             # only NULL / non-NULL is read
+                              matrix_stats=8 if (accumulate and matrix) else None)
+    return int(lib().tecm_temporal_attention_ws_floats(C.byref(a)))
+
+
+def temporal_attention(qkv: torch.Tensor, B: int, T: int, N: int, heads: int, D: int, *,
+                       probs: Optional[torch.Tensor] = None, nodes: Optional[torch.Tensor] = None,
+                       node_stats: Optional[torch.Tensor] = None, lag_stats: Optional[torch.Tensor] = None,
+                       matrix_stats: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                       groups: Optional[torch.Tensor] = None, layer: int = 0, count: bool = False, err_flag: int = 0,
+                       max_ws_bytes: Optional[int] = None) -> None:
+    """tecm_temporal_attention (include/tecmollm.h, csrc/attention_probs.hip) on one layer's `qkv` (B*T*N, 3*D), fp32 or bf16,
+    as `attention_fwd` reads it.  `probs` (B, Ns, heads, T, T) float32 receives the causal attention probabilities of the
+    nodes `nodes` (int32 (Ns), None: all N); `node_stats` (G, Ly, 4, N, heads), `lag_stats` (G, Ly, heads, T), optionally
+    `matrix_stats` (G, Ly, heads, T, T) float64 and, with `count`, `counts` (G) int64 are added to at layer slot `layer`, with
+    `groups` (B) int32 naming every window's group (an id outside [0, G) skips the window and sets TECM_BAD_GROUP in the error
+    word `err_flag` points to; 0: the device's own, `devcheck.error_word`).  `max_ws_bytes` caps the workspace (it must hold one window): the call
+    then walks more chunks of windows and returns the same bits."""
+    if qkv.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.TecmError(f"qkv must be float32 or bfloat16 (got {qkv.dtype})")
+    _lib.require_gpu_tensor(qkv, "qkv", qkv.dtype)
+    if qkv.numel() != B * T * N * 3 * D or not qkv.is_contiguous():
+        raise ValueError(f"qkv must be a contiguous ({B * T * N}, {3 * D}) tensor, got {tuple(qkv.shape)}")
+    Ns = N if nodes is None else int(nodes.numel())
+    for name, t, shape, dtype in (("probs", probs, (B, Ns, heads, T, T), torch.float32), ("nodes", nodes, (Ns,), torch.int32),
+                                  ("groups", groups, (B,), torch.int32)):
+        if t is not None:
+            _lib.require_gpu_tensor(t, name, dtype)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+    ng = ly = 0
+    if node_stats is not None:
+        ng, ly = int(node_stats.shape[0]), int(node_stats.shape[1])
+        for name, t, shape, dtype in (("node_stats", node_stats, (ng, ly, 4, N, heads), torch.float64),
+                                      ("lag_stats", lag_stats, (ng, ly, heads, T), torch.float64),
+                                      ("counts", counts, (ng,), torch.int64)):
+            if t is None:
+                raise ValueError("the statistics need node_stats, lag_stats and counts together")
+            _lib.require_gpu_tensor(t, name, dtype)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+        if matrix_stats is not None:
+            _lib.require_gpu_tensor(matrix_stats, "matrix_stats", torch.float64)
+            if tuple(matrix_stats.shape) != (ng, ly, heads, T, T) or not matrix_stats.is_contiguous():
+                raise ValueError(f"matrix_stats must be a contiguous {(ng, ly, heads, T, T)} tensor")
+    elif matrix_stats is not None:
+        raise ValueError("matrix_stats needs node_stats, lag_stats and counts")
+    if node_stats is not None and not err_flag:
+        from . import devcheck                                  # the device's sticky error word (check_device_errors reads it)
+        err_flag = devcheck.error_word(qkv.device).ptr()
+    flags = (ATT_QKV_BF16 if qkv.dtype == torch.bfloat16 else 0) | (_lib.TECM_TATT_COUNT if count else 0)
+    a = _lib.TecmTemporalAttn(qkv=qkv.data_ptr(), probs=ptr(probs), nodes=ptr(nodes), node_stats=ptr(node_stats),
+                              lag_stats=ptr(lag_stats), matrix_stats=ptr(matrix_stats), counts=ptr(counts), group=ptr(groups),
+                              err_flag=err_flag or None, B=B, T=T, N=N, heads=heads, D=D, Ns=Ns, num_groups=ng,
+                              num_layers=ly, layer=int(layer), flags=flags)
+    nws = int(lib().tecm_temporal_attention_ws_floats(C.byref(a)))
+    ws = None
+    if nws > 0 and node_stats is not None:
+        if max_ws_bytes is not None:
+            nws = min(nws, int(max_ws_bytes) // 4)
+        ws = torch.empty(nws, device=qkv.device, dtype=torch.float32)
+        a.ws, a.ws_floats = ws.data_ptr(), nws
+    check(lib().tecm_temporal_attention(C.byref(a), stream_ptr()), "tecm_temporal_attention")
+
+
 def colsum(inp: torch.Tensor, ld: int, outer: int, inner: int, nseg: int, Cn: int, *, in_off: int = 0,
            scale: float = 1.0, in_drop: Optional[TecmDrop] = None, out: Optional[torch.Tensor] = None,
            accumulate: bool = False, twin: Optional[torch.Tensor] = None) -> torch.Tensor:

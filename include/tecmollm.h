@@ -1007,6 +1007,77 @@ typedef struct {
 } TecmSarForecast;
 int tecm_sar_forecast(const TecmSarForecast* f, void* stream);
 
+/* (8) the raw-data stage on the device (scripts/preprocess.py over src/features/feature_engineering.py).
+ *
+ * (a) tecm_moments: what StandardScaler.fit computes (feature_engineering.py:161-170 for X, preprocess.py:56-60 for Y)
+ *     over a strided 2-D view src[r*ld + c], r < rows, c < cols, float32 (src_f64 = 0) or float64 (src_f64 = 1):
+ *       pool = 1  one statistic over every column (TEC: the reference reshapes to one feature)
+ *       pool = 0  one statistic per column (cols of them)
+ *       taps = 0  every row has weight 1
+ *       taps = H  row r has the integer weight  w_r = max(0, min(H-1, r-1) - max(0, r - rows + H) + 1):  the number of
+ *                 times construct_target_tensor_Y (feature_engineering.py:55-67) writes row r into Y (rows - H, ..., H), so
+ *                 that the fit equals StandardScaler().fit(Y.reshape(-1, 1)) without the H-fold tensor.  Needs taps < rows.
+ *     Per statistic, on the device:  count (int64) = sum of w over the non-NaN entries (NaN entries are skipped, as
+ *     sklearn's nansum does), mean (fp64) = sum w x / count, var (fp64) = sum w (x - mean)^2 / count (population); a
+ *     statistic with count 0 gets NaN mean and var.  Two passes, the mean stays on the device in between; no host
+ *     synchronisation, no atomics, a fixed combination order: the same bits on every call.
+ *     Accuracy contract: every thread adds its entries through a cascade of seven accumulators that carry every 64 adds
+ *     (at most 63 dependent additions per level, 16 on the last: rows*cols < 2^40), a block joins its 256 threads by a
+ *     tree of 8, and one block joins the at most TECM_MOMENTS_MAX_BLOCKS partials of a statistic by 8 sequential adds
+ *     and a tree of 8: fewer than 512 dependent fp64 additions into any output, under the 4096 the bound of
+ *     4096 * 2^-53 = 4.6e-13 (relative to the mean of |x|, and of (x - mean)^2) allows.
+ *     ws: tecm_moments_ws_bytes() bytes, 8-byte aligned (pure host arithmetic; -1 on a bad descriptor). */
+#define TECM_MOMENTS_MAX_BLOCKS 2048
+typedef struct {
+  const void* src; int64_t rows, cols, ld;
+  int32_t src_f64, pool, taps, _pad;
+  int64_t* count; double* mean; double* var;
+  void* ws;
+} TecmMoments;
+int64_t tecm_moments_ws_bytes(const TecmMoments* m);
+int tecm_moments(const TecmMoments* m, void* stream);
+
+/* (b) tecm_features_build: construct_feature_tensor_X, construct_target_tensor_Y (feature_engineering.py:38-67),
+ *     standardize_features (:179-192) and the Y scaling of preprocess.py:75-83 for one split in one call, from
+ *     tec (rows, N) float32 / float64 (tec_f64) and idx (rows, Ci) float32 / float64 (idx_f64) on the device; mean and
+ *     scale are HOST arrays of 1 + Ci doubles (the fitted feature scaler), ymean / yscale the target scaler.  Outputs, all
+ *     float32, contiguous, each optional (NULL skips it):
+ *       X  (x_rows, N, 1 + Ci)   X[t, n, 0] = f32((f64(tec[t, n]) - mean[0]) / scale[0])
+ *                                X[t, n, 1 + k] = f32((f64(idx[t, k]) - mean[1 + k]) / scale[1 + k])       x_rows <= rows
+ *       Ys (rows, N)             Ys[t, n] = f32((f64(tec[t, n]) - ymean) / yscale)
+ *       Y  (rows - H, N, H)      Y[t, n, h] = the Ys value of tec[t + 1 + h, n]: the reference's materialised layout
+ *     Exactly one fp64 subtraction, one correctly rounded fp64 division and one round-to-nearest-even conversion per value
+ *     (no reciprocal, no contraction): the bits StandardScaler.transform followed by .float() gives.  NaN passes through.
+ *     Threads run along consecutive output floats; float4 stores on 16-byte aligned quads of the output with scalar stores
+ *     for the quads a row boundary cuts, scalar everywhere for a pointer that is not 16-byte aligned.
+ *     Limits: 0 <= Ci <= TECM_FEATURES_MAX_CI, every scale non-zero, 0 < H < rows with Y. */
+#define TECM_FEATURES_MAX_CI 15
+typedef struct {
+  const void* tec; const void* idx;
+  int64_t rows, x_rows; int32_t N, Ci, H, tec_f64, idx_f64, _pad;
+  const double* mean; const double* scale;
+  double ymean, yscale;
+  float* X; float* Ys; float* Y;
+} TecmFeaturesBuild;
+int tecm_features_build(const TecmFeaturesBuild* f, void* stream);
+
+/* (c) tecm_window_batch_series: tecm_window_batch (4) with the target taken from the target-scaled series Ys (Ty, N)
+ *     instead of the reference's materialised Y (src/data/dataset.py:88-93 reads Y[a + L_in - 1], which
+ *     feature_engineering.py:63-65 filled with rows a + L_in .. a + L_in + L_out - 1 of the series):
+ *       x_out, tf_out   as in (4)
+ *       y_out[b, h, :]  = Ys[starts[b] + L_in + h, :]           h < L_out      (B, L_out, N)
+ *     so one resident series serves every L_out and a batch's target is L_out contiguous row copies.  With
+ *     starts_host_check the host rejects a window outside [0, T - L_in] and, with y_out, one whose last target row
+ *     starts[b] + L_in + L_out - 1 lies outside the Ty rows of Ys. */
+typedef struct {
+  const float* X; const float* TF; const float* Ys; const int64_t* starts;
+  const int64_t* starts_host_check;
+  int64_t T; int64_t Ty; int64_t row; /* N*C floats per time step of X */
+  int32_t N, L_in, L_out, F_t, B, _pad;
+  float* x_out; float* tf_out; float* y_out;
+} TecmWindowBatchSeries;
+int tecm_window_batch_series(const TecmWindowBatchSeries* w, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

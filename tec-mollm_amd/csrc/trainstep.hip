@@ -281,3 +281,35 @@ extern "C" int tecm_window_batch(const TecmWindowBatch* w, void* stream) {
   }
   return TECM_OK;
 }
+
+// The target from the series: y_out[b, h, :] = Ys[starts[b] + L_in + h, :] is the row copy of window_x_kernel over a
+// series that begins L_in rows later, with L_out rows a window.
+extern "C" int tecm_window_batch_series(const TecmWindowBatchSeries* w, void* stream) {
+  TECM_REQUIRE(w, TECM_E_ARG, "tecm_window_batch_series: null descriptor");
+  TECM_REQUIRE(w->X && w->starts && w->x_out, TECM_E_ARG, "tecm_window_batch_series: null pointer");
+  TECM_REQUIRE(w->T > 0 && w->row > 0 && w->N > 0 && w->L_in > 0 && w->B > 0 && w->B * (int64_t)w->L_in <= 65535,
+               TECM_E_ARG, "tecm_window_batch_series: bad shape (B*L_in must be <= 65535)");
+  TECM_REQUIRE(!w->tf_out || (w->TF && w->F_t > 0 && w->F_t <= 256), TECM_E_ARG,
+               "tecm_window_batch_series: time features need TF and 0 < F_t <= 256");
+  TECM_REQUIRE(!w->y_out || (w->Ys && w->Ty > 0 && w->L_out > 0 && w->B * (int64_t)w->L_out <= 65535), TECM_E_ARG,
+               "tecm_window_batch_series: targets need Ys, Ty > 0 and 0 < B*L_out <= 65535");
+  if (w->starts_host_check) {
+    for (int b = 0; b < w->B; ++b) {
+      const int64_t a = w->starts_host_check[b];
+      TECM_REQUIRE(a >= 0 && a + w->L_in <= w->T, TECM_E_ARG,
+                   "tecm_window_batch_series: window %d starts at %lld, outside [0, T - L_in]", b, (long long)a);
+      TECM_REQUIRE(!w->y_out || a + w->L_in + w->L_out <= w->Ty, TECM_E_ARG,
+                   "tecm_window_batch_series: window %d starts at %lld, its last target row lies outside the series", b,
+                   (long long)a);
+    }
+  }
+  TecmWindowBatch x = {};
+  x.X = w->X; x.TF = w->TF; x.starts = w->starts; x.T = w->T; x.row = w->row; x.N = w->N; x.L_in = w->L_in;
+  x.L_out = w->L_out; x.F_t = w->F_t; x.B = w->B; x.x_out = w->x_out; x.tf_out = w->tf_out;
+  const int rc = tecm_window_batch(&x, stream);                     // starts already checked above
+  if (rc != TECM_OK || !w->y_out) return rc;
+  TecmWindowBatch y = {};
+  y.X = w->Ys + (int64_t)w->L_in * w->N; y.starts = w->starts; y.T = w->Ty - w->L_in; y.row = w->N; y.N = w->N;
+  y.L_in = w->L_out; y.B = w->B; y.x_out = w->y_out;
+  return tecm_window_batch(&y, stream);
+}

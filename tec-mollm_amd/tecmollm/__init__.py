@@ -4,8 +4,10 @@ Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
   csrc/            hand-written HIP kernels + the C ABI (include/tecmollm.h at the repo root)
   tecmollm/        ctypes binding, autograd stage functions, graph preparation, training-step helpers, test-split evaluation,
                    input attribution, ensemble forecasts and their scores, spatial and temporal attention maps, conformal
-                   prediction intervals
+                   prediction intervals, raw-data preprocessing
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
+  src/features/    mirror of the reference's feature engineering (`from src.features.feature_engineering import ...`)
+  src/data/        mirrors of the reference's dataset and data loader, and the series-backed SeriesWindowDataset
   src/models/      mirror of the reference's baselines (`from src.models.baselines import HistoricalAverage`)
 """
 from ._lib import LIB_PATH, TecmError, lib  # noqa: F401
@@ -22,6 +24,8 @@ from .spatial_attention import (AttentionStats, attention_maps, evaluate_attenti
                                 graph_groups_by_sample, graph_groups_by_slot, spatial_attention, write_attention)
 from .temporal_attention import (TemporalAttentionStats, evaluate_temporal_attention, temporal_attention,  # noqa: F401
                                  write_temporal_attention)
+from . import preprocess  # noqa: F401
+from .preprocess import DeviceStandardScaler, preprocess_splits  # noqa: F401
 
 __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradient", "integrated_gradients",
            "attribution_maps", "write_attributions", "dropout_seed", "ensemble", "member_seed", "ensemble_members",
@@ -29,4 +33,5 @@ __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradien
            "evaluate_attention", "attention_maps", "write_attention", "graph_groups_by_sample", "graph_groups_by_slot",
            "graph_groups_by_lag", "conformal", "conformal_ranks", "ConformalCalibrator", "ConformalIntervals",
            "calibrate_conformal", "conformal_forecast", "evaluate_conformal", "write_conformal", "temporal_attention",
-           "TemporalAttentionStats", "evaluate_temporal_attention", "write_temporal_attention"]
+           "TemporalAttentionStats", "evaluate_temporal_attention", "write_temporal_attention", "preprocess", "DeviceStandardScaler",
+           "preprocess_splits"]

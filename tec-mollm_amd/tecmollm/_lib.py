@@ -245,6 +245,36 @@ class TecmSarForecast(C.Structure):
     ]
 
 
+class TecmMoments(C.Structure):
+    _fields_ = [
+        ("src", C.c_void_p), ("rows", C.c_int64), ("cols", C.c_int64), ("ld", C.c_int64),
+        ("src_f64", C.c_int32), ("pool", C.c_int32), ("taps", C.c_int32), ("_pad", C.c_int32),
+        ("count", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
+        ("ws", C.c_void_p),
+    ]
+
+
+class TecmFeaturesBuild(C.Structure):
+    _fields_ = [
+        ("tec", C.c_void_p), ("idx", C.c_void_p),
+        ("rows", C.c_int64), ("x_rows", C.c_int64), ("N", C.c_int32), ("Ci", C.c_int32), ("H", C.c_int32),
+        ("tec_f64", C.c_int32), ("idx_f64", C.c_int32), ("_pad", C.c_int32),
+        ("mean", C.POINTER(C.c_double)), ("scale", C.POINTER(C.c_double)),
+        ("ymean", C.c_double), ("yscale", C.c_double),
+        ("X", c_f32p), ("Ys", c_f32p), ("Y", c_f32p),
+    ]
+
+
+class TecmWindowBatchSeries(C.Structure):
+    _fields_ = [
+        ("X", c_f32p), ("TF", c_f32p), ("Ys", c_f32p), ("starts", C.c_void_p), ("starts_host_check", C.c_void_p),
+        ("T", C.c_int64), ("Ty", C.c_int64), ("row", C.c_int64),
+        ("N", C.c_int32), ("L_in", C.c_int32), ("L_out", C.c_int32), ("F_t", C.c_int32), ("B", C.c_int32),
+        ("_pad", C.c_int32),
+        ("x_out", c_f32p), ("tf_out", c_f32p), ("y_out", c_f32p),
+    ]
+
+
 class TecmConvDx(C.Structure):
     _fields_ = [("dy", C.c_void_p), ("wpack", C.c_void_p), ("dinp", c_f32p),
                 ("B", C.c_int32), ("Lc", C.c_int32), ("N", C.c_int32), ("Cout", C.c_int32), ("ld_in", C.c_int32),
@@ -277,6 +307,8 @@ TECM_TATT_COUNT = 8
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
 TECM_SAR_MAX_K, TECM_SAR_MAX_LAG, TECM_SAR_MAX_LONG_AR, TECM_SAR_MAX_OFFSET, TECM_SAR_CHUNK = 12, 32, 64, 64, 1024
 TECM_SAR_DEGENERATE, TECM_SAR_NONFINITE, TECM_SAR_MA_DROPPED = 1, 2, 4
+TECM_MOMENTS_MAX_BLOCKS = 2048
+TECM_FEATURES_MAX_CI = 15
 
 
 EXPORTS = {
@@ -383,6 +415,10 @@ EXPORTS = {
     "tecm_sar_fit": (C.c_int, [C.POINTER(TecmSarFit), C.c_void_p]),
     "tecm_sar_solve": (C.c_int, [C.POINTER(TecmSarFit), C.c_void_p]),
     "tecm_sar_forecast": (C.c_int, [C.POINTER(TecmSarForecast), C.c_void_p]),
+    "tecm_moments_ws_bytes": (C.c_int64, [C.POINTER(TecmMoments)]),
+    "tecm_moments": (C.c_int, [C.POINTER(TecmMoments), C.c_void_p]),
+    "tecm_features_build": (C.c_int, [C.POINTER(TecmFeaturesBuild), C.c_void_p]),
+    "tecm_window_batch_series": (C.c_int, [C.POINTER(TecmWindowBatchSeries), C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -598,6 +598,11 @@ int tecm_conv_dx_f32(const TecmConvDx* p, void* stream);
  * the shapes these kernels refuse to the window-view GEMMs (tecm_gemm_*) instead of failing with TECM_E_LDS. */
 int tecm_conv_fwd_supported(int32_t Lc, int32_t Cout, int32_t ld_in, int32_t f32);
 int tecm_conv_dx_supported(int32_t Lc, int32_t Cout, int32_t ld_in, int32_t f32);
+/* Time steps per sequence tile (TC) the launcher of that shape will use -- a sequence is walked in chunks of TC steps, the last
+ * one shorter where TC does not divide Lc -- from the same plan code the launchers call; 0 where the predicate above says no.
+ * Pure host arithmetic.  (tecm_conv_dw_* walks fixed chunks of 24 steps.) */
+int tecm_conv_fwd_tile_steps(int32_t Lc, int32_t Cout, int32_t ld_in, int32_t f32);
+int tecm_conv_dx_tile_steps(int32_t Lc, int32_t Cout, int32_t ld_in, int32_t f32);
 /* 1 when one forward tile holds a whole sequence of Lc steps -- the condition for TecmConvFwd::stats -- else 0.  Pure host
  * function. */
 int tecm_conv_fwd_stats_supported(int32_t Lc);
@@ -608,7 +613,9 @@ int tecm_conv_fwd_stats_supported(int32_t Lc);
  * inp bf16 (B, Lc, N, ld_in), dy bf16 (B, Lc, N, 3*Cout), dw3 / dw5 / dw7 fp32 (Cout, Cin, 3 / 5 / 7) -- only the Cin
  * real channels are written.  A persistent kernel of num_blocks thread blocks (one per CU is the intended use) keeps
  * all 15 taps' accumulators in registers and leaves one slab per block in `workspace`
- * (tecm_conv_dw_workspace(Cout, ld_in, num_blocks) floats); a second kernel adds the slabs in a fixed order.
+ * (tecm_conv_dw_workspace(Cout, ld_in, num_blocks) floats); a second kernel adds the slabs in a fixed order.  Where a tile is
+ * shared by two blocks (ld_in 64, Cout 128: each takes half the output channels) num_blocks = 1 launches the two, as the
+ * workspace query sizes for.
  * (ld_in, Cout) in {24, 64} x {64, 128}; Lc % 4 == 0; 16-byte aligned tensors. */
 typedef struct TecmConvDw {
   const void* inp;

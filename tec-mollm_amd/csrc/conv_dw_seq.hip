@@ -379,9 +379,11 @@ int launch(const TecmConvDw* p, hipStream_t st) {
   a.ntiles = (int)tiles;
   const size_t lds = (size_t)G::XBYTES + G::YBYTES;
   static_assert(G::XBYTES + G::YBYTES <= 160 * 1024, "one tile must fit the LDS");
-  int nbf = p->num_blocks / G::F;                           // blocks per flavor
+  // blocks per flavor: at least one, as tecm_conv_dw_workspace sizes the slabs (num_blocks = 1 where a tile takes two
+  // flavors launches two blocks; refusing it made TECM_CONV_DW_BLOCKS=1 an error on the 64 -> 128 block only)
+  int nbf = p->num_blocks / G::F;
+  if (nbf < 1) nbf = 1;
   if (nbf > tiles) nbf = (int)tiles;
-  TECM_REQUIRE(nbf >= 1, TECM_E_ARG, "tecm_conv_dw_bf16: num_blocks must be at least %d", G::F);
   // per launch, not once per process: the attribute belongs to the function ON THE CURRENT DEVICE (see conv_seq.hip)
   TECM_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dw_seq_kernel<LD_IN, COUT, PD, F32>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess,

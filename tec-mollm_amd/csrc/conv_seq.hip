@@ -886,6 +886,14 @@ extern "C" int tecm_conv_fwd_supported(int32_t Lc, int32_t Cout, int32_t ld_in, 
   return conv_fwd_lds(Lc, ld_in, f32 != 0, nullptr, nullptr) <= 64 * 1024 ? 1 : 0;
 }
 
+// time steps per forward tile (the TC of conv_fwd_launch: chunks of TC, a shorter last one), 0 where the predicate refuses
+extern "C" int tecm_conv_fwd_tile_steps(int32_t Lc, int32_t Cout, int32_t ld_in, int32_t f32) {
+  if (!tecm_conv_fwd_supported(Lc, Cout, ld_in, f32)) return 0;
+  int TC = 0;
+  conv_fwd_lds(Lc, ld_in, f32 != 0, nullptr, &TC);
+  return TC;
+}
+
 // 1 when one forward tile holds a whole sequence of Lc steps, so that tecm_conv_fwd_bf16 can compute TecmConvFwd::stats, else 0
 extern "C" int tecm_conv_fwd_stats_supported(int32_t Lc) { return Lc > 0 && Lc <= 8 * tecm_convseq::MAXT ? 1 : 0; }
 
@@ -999,6 +1007,12 @@ static ConvDxPlan conv_dx_plan(int Lc, int Cout, int ld_in, bool f32) {
 extern "C" int tecm_conv_dx_supported(int32_t Lc, int32_t Cout, int32_t ld_in, int32_t f32) {
   if (Lc <= 0 || Lc % 8 != 0 || Cout <= 0 || Cout % 64 != 0 || ld_in <= 0 || ld_in % 4 != 0 || ld_in > 64) return 0;
   return conv_dx_plan(Lc, Cout, ld_in, f32 != 0).lds <= 160 * 1024 ? 1 : 0;
+}
+
+// time steps per d-input tile (the TC of conv_dx_launch, after the LDS cap), 0 where the predicate refuses
+extern "C" int tecm_conv_dx_tile_steps(int32_t Lc, int32_t Cout, int32_t ld_in, int32_t f32) {
+  if (!tecm_conv_dx_supported(Lc, Cout, ld_in, f32)) return 0;
+  return conv_dx_plan(Lc, Cout, ld_in, f32 != 0).TC;
 }
 
 static int conv_dx_launch(const TecmConvDx* p, void* stream, bool f32, const char* who) {

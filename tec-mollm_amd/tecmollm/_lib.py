@@ -392,6 +392,8 @@ EXPORTS = {
     "tecm_gemm_tile_of_block": (None, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tecm_gemm_tiles_of_blocks": (None, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "tecm_conv_dx_supported": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tecm_conv_fwd_tile_steps": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "tecm_conv_dx_tile_steps": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "tecm_transpose_scale": (C.c_int, [c_f32p, C.c_int64, c_f32p, C.c_int64, C.c_int32, C.c_int32, C.c_float,
                                        C.c_void_p]),
     "tecm_weight_bf16": (C.c_int, [c_f32p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,

@@ -55,6 +55,43 @@ def test_full_step_over_model_configurations(dev, name, kw, over, prec, train):
         assert_parity(res, small24=True)
 
 
+# Widths the conv sequence kernels' predicates admit in part -- and the model does not: Multi_Scale_Conv_Block takes out_channels
+# 64, 128 and 256 only (the GroupNorm kernels work on 64-channel chunks) and says so when it is built.  No full step exists to
+# compare; what is pinned is the loud refusal, and what the predicates would route where.
+REFUSED_CHANNEL_LISTS = [("ch32_96", {"temporal_channel_list": [32, 96]}), ("ch64_192", {"temporal_channel_list": [64, 192]})]
+
+
+@pytest.mark.parametrize("name,over", REFUSED_CHANNEL_LISTS, ids=[c[0] for c in REFUSED_CHANNEL_LISTS])
+@pytest.mark.parametrize("prec", ["fp32", "bf16"])
+def test_channel_widths_the_groupnorm_stage_is_not_built_for_fail_loudly(dev, name, over, prec):
+    """temporal_channel_list [32, 96] and [64, 192]: the model's constructor raises, naming out_channels, before any kernel runs --
+    the stage neither falls back nor mis-computes.  The conv kernels' instantiations for 32, 96 and 192 channels are therefore
+    reached through the C ABI only (tests/test_gpu_conv_seq_domain.py)."""
+    cfg = R.default_config(num_nodes=12)
+    cfg.update(over)
+    with pytest.raises(ValueError, match="out_channels must be 64, 128 or 256"):
+        compare_forward_backward(cfg, B=2, grid=(3, 4), threshold_km=170.0, gat_graphs="per_timestep", seed=5, precision=prec)
+
+
+@pytest.mark.parametrize("chans,fwd,dx,dw", [([32, 96], (True, True), (False, False), (False, False)),
+                                             ([64, 192], (True, False), (True, True), (True, False))],
+                         ids=["ch32_96", "ch64_192"])
+def test_channel_lists_meet_the_kernels_their_names_promise(dev, chans, fwd, dx, dw):
+    """What WOULD serve the two conv blocks of ch32_96 and ch64_192 at the sweep's shapes (L_in = 48, strides 2, 2; block 0 reads
+    the 22 spatial channels at a pitch of 24), in fp32 and in bf16 alike: [32, 96] runs the forward's 3- and 9-unit
+    assignments and takes the window-view GEMMs for both gradients (the d-input kernel wants multiples of 64, the
+    weight-gradient kernel its four built pairs); [64, 192] runs the d-input kernel at 192 channels and takes the GEMMs for
+    the forward (more than 128 channels) and the weight gradient of its second block."""
+    from tecmollm import ops
+    cfg = R.default_config(num_nodes=12)
+    L = cfg["temporal_seq_len"]
+    blocks = [(L, chans[0], 24), (L // cfg["temporal_strides"][0], chans[1], chans[0])]
+    for f32 in (True, False):
+        assert tuple(ops.conv_fwd_seq_ok(*b, f32=f32) for b in blocks) == fwd
+        assert tuple(ops.conv_dx_seq_ok(*b, f32=f32) for b in blocks) == dx
+    assert tuple(ops.conv_dw_seq_ok(*b) for b in blocks) == dw
+
+
 def test_unsupported_feature_width_fails_loudly(dev):
     """C = C_in + d_emb != 22 is the one configuration the kernels are not built for: it must raise, not mis-compute."""
     from tecmollm import TecmError

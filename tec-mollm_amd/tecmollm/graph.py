@@ -119,6 +119,9 @@ def csr_by_source(rowptr: np.ndarray, colidx: np.ndarray, num_nodes: int):
 
 
 MAX_WINDOW = 512    # the backward's by-source pass: two rounds of 256 rows
+# The ladder `build` walks, largest first.  110 is the 41 x 71 grid's size (256 rows).  Every rung is reachable:
+# tests/test_host_spatial_tiling.py pins a graph for each, tests/test_gpu_spatial_tiling.py runs the kernels on them.
+TILE_SIZES = (128, 120, 112, 110, 104, 96, 80, 64, 48, 32, 16, 8, 4, 2, 1)
 
 
 def lds_bytes_fwd(win: int, tile_nodes: int, tile_edges: int = 0) -> int:
@@ -139,7 +142,7 @@ def build(edge_index: torch.Tensor, num_nodes: int, device: torch.device, demb: 
     # rows are preferred -- the backward's by-source pass then is one round per item and keeps its d x_l sums in half
     # the registers -- as long as that costs less than a quarter of the tile (the 41 x 71 grid: 110 nodes, 256 rows).
     chosen, wide = None, None
-    for tn in (128, 120, 112, 110, 104, 96, 80, 64, 48, 32, 16, 8, 4, 2, 1):
+    for tn in TILE_SIZES:
         lo, hi = tile_windows(rowptr, colidx, num_nodes, tn)
         wmax = int((hi - lo).max())
         bounds = np.minimum(np.arange(lo.size + 1) * tn, num_nodes)

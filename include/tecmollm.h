@@ -897,6 +897,57 @@ typedef struct {
 } TecmIntervalStats;
 int tecm_interval_stats(const TecmIntervalStats* c, void* stream);
 
+/* (3h) significance of the comparison: the eight statistics of (3) kept per WINDOW (a), and paired circular block-bootstrap
+ * sums over such a table (b).  Float64 additions in a fixed, documented order, no atomics on any sum: the same call gives the
+ * same bits, and tests/significance_ref.py restates both addition by addition.
+ *
+ * (a) tecm_metrics_window: operands, strides and value pipeline of (3) / (3b).  For every sample s and horizon h the eight
+ *     statistics summed over all I nodes are WRITTEN (not accumulated) to
+ *       table[(row*H + h)*8 + k],   row = rows[s] (int64, on the device), or row0 + s when rows is NULL,
+ *     a table of table_rows x H x 8 doubles.  Rows that no sample names are not touched; two samples naming one row leave
+ *     either.  A row outside [0, table_rows) writes nothing and sets TECM_BAD_ROW in *err_flag (never NULL, sticky).
+ *     Order of the sum of one (s, h): lane l = i mod 64 of a wave adds its nodes i = l, l + 64, l + 128, ... in ascending
+ *     order into a partial starting at +0.0; the 64 partials are then halved five times and once more: x[l] += x[l ^ o] for
+ *     o = 32, 16, 8, 4, 2, 1 (a lane without a node holds +0.0).
+ *     An operand with stride_i == 1 (stride_h may be 0) is read in place; one with stride_h == 1 and stride_i == H goes
+ *     through a padded LDS tile when 1 < H <= TECM_MAP_LDS_MAX_H, as in (3b); everything else is read in place.
+ *     Limits: S < 2^31, ceil(H / 4) <= 65535, scale != 0. */
+#define TECM_BAD_ROW 32
+#define TECM_BAD_START 64
+typedef struct {
+  const float* pred; int64_t p_stride_s, p_stride_h, p_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  int64_t S; int32_t H; int32_t _pad; int64_t I;      /* samples, horizons, nodes */
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  int32_t _pad2;
+  double* table; int64_t table_rows;
+  const int64_t* rows; int64_t row0;
+  int32_t* err_flag;
+} TecmMetricsWindow;
+int tecm_metrics_window(const TecmMetricsWindow* m, void* stream);
+
+/* (b) tecm_block_bootstrap: table (M, S, W) doubles at table[m*stride_m + s*stride_s + w] (rows W-contiguous, stride_s >= W),
+ *     starts (R, K) int32 with K == ceil(S / L), L = block length >= 1, group (S) int32 in [0, G) or NULL (group 0):
+ *       out[((r*M + m)*G + g)*W + w] = sum over the positions t = 0 .. S-1, in ascending t, of table[m, row(r, t), w] for
+ *       those t with group[row(r, t)] == g,   row(r, t) = (starts[r*K + t / L] + t mod L) mod S
+ *     -- the circular block bootstrap, the last block truncated so that exactly S windows are read; ONE running float64 sum
+ *     per output value starting at +0.0, so a sequential restatement matches bit for bit.  Every m is resampled with the
+ *     same starts (paired).  A group that does not occur yields zeros; every output value is written.  A start outside
+ *     [0, S) skips its block's windows and sets TECM_BAD_START, a group id outside [0, G) skips the window and sets
+ *     TECM_BAD_GROUP, both in *err_flag.
+ *     Limits: 0 < S < 2^31, 0 < R < 2^31, 1 <= G <= 65535, M * G * ceil(W / 64) <= 65535 (one grid dimension): any W and
+ *     G <= 16 up to M = 585 at W = 400. */
+typedef struct {
+  const double* table; int64_t stride_m, stride_s;
+  int64_t M, S, W;
+  const int32_t* group; int32_t G; int32_t _pad;
+  const int32_t* starts; int64_t R, K, L;
+  double* out;
+  int32_t* err_flag;
+} TecmBlockBootstrap;
+int tecm_block_bootstrap(const TecmBlockBootstrap* b, void* stream);
+
 /* (4) sliding-window batch assembly from device-resident series (SlidingWindowSamplerDataset.__getitem__
  * src/data/dataset.py:65-99 + the harness reshapes train.py:62-65, :76): for sample b with window
  * start a = starts[b] (already multiplied by the dataset stride):

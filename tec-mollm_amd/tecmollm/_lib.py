@@ -195,6 +195,28 @@ class TecmIntervalStats(C.Structure):
     ]
 
 
+class TecmMetricsWindow(C.Structure):
+    _fields_ = [
+        ("pred", c_f32p), ("p_stride_s", C.c_int64), ("p_stride_h", C.c_int64), ("p_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("_pad", C.c_int32), ("I", C.c_int64),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("_pad2", C.c_int32),
+        ("table", C.c_void_p), ("table_rows", C.c_int64), ("rows", C.c_void_p), ("row0", C.c_int64),
+        ("err_flag", C.c_void_p),
+    ]
+
+
+class TecmBlockBootstrap(C.Structure):
+    _fields_ = [
+        ("table", C.c_void_p), ("stride_m", C.c_int64), ("stride_s", C.c_int64),
+        ("M", C.c_int64), ("S", C.c_int64), ("W", C.c_int64),
+        ("group", C.c_void_p), ("G", C.c_int32), ("_pad", C.c_int32),
+        ("starts", C.c_void_p), ("R", C.c_int64), ("K", C.c_int64), ("L", C.c_int64),
+        ("out", C.c_void_p), ("err_flag", C.c_void_p),
+    ]
+
+
 class TecmWindowBatch(C.Structure):
     _fields_ = [
         ("X", c_f32p), ("TF", c_f32p), ("Y", c_f32p), ("starts", C.c_void_p), ("starts_host_check", C.c_void_p),
@@ -302,6 +324,7 @@ TECM_ENS_MAX_K = 64
 TECM_CONF_ABS, TECM_CONF_SIGNED = 0, 1
 TECM_INTERVAL_STATS = 6
 TECM_SELECT_MAX_Q = 8
+TECM_BAD_ROW, TECM_BAD_START = 32, 64
 TECM_ATTN_SKIP_UNCONNECTED = 1
 TECM_TATT_COUNT = 8
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
@@ -410,6 +433,8 @@ EXPORTS = {
     "tecm_conformal_scores": (C.c_int, [C.POINTER(TecmConformalScores), C.c_void_p]),
     "tecm_column_select": (C.c_int, [C.POINTER(TecmColumnSelect), C.c_void_p]),
     "tecm_interval_stats": (C.c_int, [C.POINTER(TecmIntervalStats), C.c_void_p]),
+    "tecm_metrics_window": (C.c_int, [C.POINTER(TecmMetricsWindow), C.c_void_p]),
+    "tecm_block_bootstrap": (C.c_int, [C.POINTER(TecmBlockBootstrap), C.c_void_p]),
     "tecm_window_batch": (C.c_int, [C.POINTER(TecmWindowBatch), C.c_void_p]),
     "tecm_window_baseline": (C.c_int, [C.POINTER(TecmWindowBaseline), C.c_void_p]),
     "tecm_slot_mean": (C.c_int, [C.POINTER(TecmSlotMean), C.c_void_p]),

@@ -13,7 +13,9 @@ synchronisation to the step:
     `poll(sync=True)` waits for the copy first.
 
 Bit 4 (TECM_BAD_GROUP) is set by the per-cell evaluation statistics (`MapMetrics.update`) when a sample's group id lies
-outside [0, num_groups): the sample is skipped, and `poll()` raises `TecmError`.  Bit 16 is used by the data-parallel
+outside [0, num_groups): the sample is skipped, and `poll()` raises `TecmError`.  Bits 5 and 6 (TECM_BAD_ROW, TECM_BAD_START)
+are set by the significance kernels (`WindowScores.update`: a table row outside the table; `block_bootstrap`: a block start
+outside [0, S)) and raise `TecmError` too.  Bit 16 is used by the data-parallel
 rank-divergence check (tecmollm/train.py).
 """
 from __future__ import annotations
@@ -26,11 +28,14 @@ from ._lib import TecmError
 
 BAD_TOD, BAD_DOY, BAD_YEAR, BAD_SEASON = 1, 2, 4, 8
 BAD_GROUP = 16
+BAD_ROW, BAD_START = 32, 64
 RANKS_DIVERGED = 1 << 16
 
 _NAMES = {BAD_TOD: "time-of-day index outside [0, 12)", BAD_DOY: "day-of-year index outside [0, 366)",
           BAD_YEAR: "year index outside [0, num_years)", BAD_SEASON: "season index outside [0, 4)",
           BAD_GROUP: "group id outside [0, num_groups) (the sample was skipped)",
+          BAD_ROW: "table row outside [0, table_rows) (nothing was written)",
+          BAD_START: "bootstrap block start outside [0, S) (the block was skipped)",
           RANKS_DIVERGED: "data-parallel ranks no longer hold identical parameters"}
 
 
@@ -69,8 +74,10 @@ class DeviceErrorWord:
             self.event = None
             what = "; ".join(text for bit, text in _NAMES.items() if code & bit)
             if not (code & 15):
-                if code & BAD_GROUP:
-                    raise TecmError(f"device error word = {code:#x} (TECM_BAD_GROUP): {what}")
+                if code & (BAD_GROUP | BAD_ROW | BAD_START):
+                    flags = ", ".join(n for b, n in ((BAD_GROUP, "TECM_BAD_GROUP"), (BAD_ROW, "TECM_BAD_ROW"),
+                                                     (BAD_START, "TECM_BAD_START")) if code & b)
+                    raise TecmError(f"device error word = {code:#x} ({flags}): {what}")
                 raise RuntimeError(f"device error word = {code:#x}: {what}")
             raise IndexError(f"index out of range in self (device error word = {code:#x}): {what} -- the reference's "
                              "nn.Embedding raises here (modules.py:255-258); every output built from the bad index is NaN")

@@ -114,10 +114,11 @@ def get_baseline_predictions(test_dataset, L_in: int, L_out: int) -> np.ndarray:
 
 
 def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_weight, order, groups, num_groups,
-                per_batch=None):
+                per_batch=None, per_forecast=None):
     """The one pass over the batches that `evaluate_split`, `evaluate_maps` and `evaluate_conformal` share: every forecast
     feeds a `HorizonMetrics` of its own and, when `num_groups` is given, a `MapMetrics` too.  `per_batch(ordinal, x, tf, y,
-    out, ids)`, when given, sees every batch after its forecasts are scored.
+    out, ids)`, when given, sees every batch after its forecasts are scored; `per_forecast(name, pred, y, chunk)`, when
+    given, sees every scored forecast with its batch's dataset indices (`score_windows`).
     Returns ({name: HorizonMetrics}, {name: MapMetrics})."""
     from src.evaluation.metrics import HorizonMetrics, MapMetrics
     kinds = list(baselines)
@@ -141,6 +142,8 @@ def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_
             hms[name].update(pred, y)
             if mms:
                 mms[name].update(pred, y, ids)
+            if per_forecast is not None:
+                per_forecast(name, pred, y, chunk)
         if per_batch is not None:
             per_batch(ordinal, x, tf, y, out, ids)
     return hms, mms

@@ -1136,6 +1136,70 @@ typedef struct {
 } TecmWindowBatchSeries;
 int tecm_window_batch_series(const TecmWindowBatchSeries* w, void* stream);
 
+/* (9) LinearBaseline (not in the reference, whose PRD section 3 calls its baseline zoo extensible): a direct linear map from
+ * the input window to the H targets, fitted per node by ridge regression -- the "Linear" family of the LLM-forecaster
+ * ablations.  The first baseline here that is FITTED against the target-scaled series; (5) reads the feature-scaled channel
+ * as it is.  Everything below is fp64; X and ys are fp32.
+ *   predictors  z = [1, X[a + L_in - lag[p], n, chan[p]] for p = 1 .. P-1] for the window that starts at row a: P counts the
+ *               intercept, entry 0 of chan / lag is ignored, 1 <= lag[p] <= min(L_in, TECM_LIN_MAX_LAG) (lag 1 is the last
+ *               input step), 0 <= chan[p] < C with at most TECM_LIN_MAX_CHANNELS distinct channels.
+ *   targets     y_h = ys[(a + L_in + h) * ys_stride_t + n * ys_stride_n], h < H (element strides, Ty rows).
+ *   windows     a = first + i * step, i < count: an arithmetic progression, first >= 0, step >= 1, count >= 1, the last
+ *               window's inputs inside the T rows of X and its targets inside the Ty rows of ys.
+ *   model       W_n = argmin sum_a |y - z^T W|^2 + alpha sum_{p >= 1} |W_p|^2 (the intercept is not penalised): sklearn's
+ *               Ridge(alpha, fit_intercept=True) in exact arithmetic.  Pooled: one W from the sum of the nodes' normal
+ *               equations.
+ * tecm_lin_gram writes gram (N, P, P+H) = [G | R], G = sum_a z z^T, R = sum_a z y^T.  Every entry is ONE running fp64 sum
+ * over the windows in ascending order; the factors are fp32 values, so every product is exact in fp64 and a fused
+ * multiply-add equals multiply-then-add.  Hence no atomics, no split of the time axis and no workspace; G is bitwise
+ * symmetric (the full P x (P+H) rectangle is computed), two launches return identical bits, and a sequential loop over
+ * the windows on the host reproduces them bit for bit.  With pooled != 0 it also writes gram_pooled (P, P+H): the nodes'
+ * arrays added in ascending node order, one chain per entry.
+ * A block owns a tile of nodes for the whole series and walks it in chunks of windows staged in LDS (at most 64 KiB);
+ * tecm_lin_gram_supported is pure host arithmetic: 1 when the descriptor's shape is served (pointers are not looked at), else
+ * 0 with the reason in tecm_last_error; tile_nodes / chunk_windows (either may be NULL) receive the geometry the launch uses. */
+enum { TECM_LIN_MAX_P = 64, TECM_LIN_MAX_H = 32, TECM_LIN_MAX_LAG = 512, TECM_LIN_MAX_CHANNELS = 8 };
+enum { TECM_LIN_DEGENERATE = 1, TECM_LIN_NONFINITE = 2 };
+typedef struct {
+  const float* X; int64_t T;                    /* (T, N*C) */
+  const float* ys; int64_t ys_stride_t, ys_stride_n, Ty;
+  int32_t N, C, P, H, L_in, pooled;
+  int32_t chan[TECM_LIN_MAX_P], lag[TECM_LIN_MAX_P];
+  int64_t first, step, count;
+  double* gram;           /* (N, P, P+H) */
+  double* gram_pooled;    /* (P, P+H) when pooled */
+} TecmLinGram;
+int tecm_lin_gram_supported(const TecmLinGram* g, int32_t* tile_nodes, int32_t* chunk_windows);
+int tecm_lin_gram(const TecmLinGram* g, void* stream);
+
+/* tecm_lin_solve: for each of the N systems gram (N, P, P+H) (N = 1 for a pooled fit), the Cholesky solve of
+ * (G + alpha diag(0, 1, ..., 1)) W = R with H right-hand sides: coef (N, P, H) and, when coef_t is given, the same values
+ * node-fastest (P, H, N), the layout tecm_lin_forecast reads.  status (N): any non-finite entry of [G | R] gives
+ * TECM_LIN_NONFINITE and NaN coefficients; a pivot <= 1e-12 x its diagonal entry (of G + alpha D) gives TECM_LIN_DEGENERATE
+ * and the intercept-only model coef[0, h] = R[0, h] / G[0, 0], other rows 0: the forecast is the mean training target. */
+typedef struct {
+  const double* gram;
+  int32_t N, P, H, _pad;
+  double alpha;
+  double* coef; double* coef_t;
+  int32_t* status;
+} TecmLinSolve;
+int tecm_lin_solve(const TecmLinSolve* s, void* stream);
+
+/* tecm_lin_forecast: TecmWindowBaseline's fields (channel, mode and period unused; o_stride_h != 0 when L_out > 1; L_out is
+ * the fitted H) plus the predictor pairs and the coefficients: coef is node-fastest, coef[(p*H + h)*N + n], with
+ * coef_stride_n = 1, or one (P, H) array for every node with coef_stride_n = 0 (pooled).
+ *   out[b, h, n] = (float)(coef[0, h] + z_1 coef[1, h] + ... + z_{P-1} coef[P-1, h]), p ascending, in fp64.
+ * One launch for any number of windows; a window outside [0, T - L_in] that reaches the kernel is written as NaN, never
+ * read. */
+typedef struct {
+  TecmWindowBaseline w;
+  const double* coef; int64_t coef_stride_n;
+  int32_t P, _pad;
+  int32_t chan[TECM_LIN_MAX_P], lag[TECM_LIN_MAX_P];
+} TecmLinForecast;
+int tecm_lin_forecast(const TecmLinForecast* f, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

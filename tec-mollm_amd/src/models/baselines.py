@@ -17,6 +17,11 @@ the coefficients.  All linear algebra in fp64, no iteration, no constant term; e
 call (`tecm_sar_fit`), and every window of a test split is forecast by one launch (`tecm_sar_forecast`), which the
 reference's class cannot do at all (it forecasts from the end of the training series only).  The estimates are
 consistent but not the maximum-likelihood ones: expect coefficients and forecasts close to, not equal to, statsmodels'.
+
+`LinearBaseline` is not in the reference: a direct linear map from the input window to the L_out targets, fitted per node
+by ridge regression against the TARGET-scaled series -- the "Linear" baseline an LLM-based forecaster is asked to beat.
+The normal equations of every window of a split are accumulated on the device (`tecm_lin_gram`), solved by Cholesky
+(`tecm_lin_solve`), and every window of a test split is forecast by one launch (`tecm_lin_forecast`).
 """
 from __future__ import annotations
 
@@ -28,7 +33,8 @@ import numpy as np
 import torch
 
 from tecmollm import _lib
-from tecmollm._lib import TecmSarFit, TecmSarForecast, TecmSlotMean, TecmWindowBaseline, check, lib, require_gpu_tensor, stream_ptr
+from tecmollm._lib import (TecmLinForecast, TecmLinGram, TecmLinSolve, TecmSarFit, TecmSarForecast, TecmSlotMean,
+                           TecmWindowBaseline, check, lib, require_gpu_tensor, stream_ptr)
 
 log = logging.getLogger(__name__)
 
@@ -329,6 +335,251 @@ class SarimaBaseline:
         out = self.forecast_series(tail, [0], tail.shape[0], int(steps)).cpu().numpy().astype(np.float64)
         col = {int(n): j for j, n in enumerate(self.nodes_)}
         return {int(n): out[0, :, col[int(n)]] for n in node_indices if int(n) in col}
+
+
+# ------------------------------------------------------------------------------------ LinearBaseline
+LINEAR_DEFAULT_LAGS = 48
+
+
+def linear_pairs(lags, channel: int, exog, L_in: int):
+    """The (channel, look-back) predictor pairs of a `LinearBaseline`: `lags` of `channel` (None: 1 .. min(L_in, 48)), then
+    the `exog` pairs.  Look-back 1 is the last input step.  Raises ValueError for what no descriptor can hold; the library
+    checks the rest against the data (`tecm_lin_gram_supported`)."""
+    lags = range(1, min(int(L_in), LINEAR_DEFAULT_LAGS) + 1) if lags is None else lags
+    try:
+        pairs = [(int(channel), int(l)) for l in lags] + [(int(c), int(l)) for c, l in exog]
+    except (TypeError, ValueError):
+        raise ValueError(f"lags must be integers and exog (channel, lag) pairs, got {lags!r} and {exog!r}")
+    if len(pairs) + 1 > _lib.TECM_LIN_MAX_P:
+        raise ValueError(f"{len(pairs)} predictors and the intercept exceed {_lib.TECM_LIN_MAX_P}")
+    if len(set(pairs)) != len(pairs):
+        raise ValueError(f"a predictor pair is given twice in {pairs}")
+    for c, l in pairs:
+        if c < 0 or not 1 <= l <= _lib.TECM_LIN_MAX_LAG:
+            raise ValueError(f"pair {(c, l)}: channels must not be negative and look-backs lie in [1, {_lib.TECM_LIN_MAX_LAG}]")
+    return pairs
+
+
+def _pair_arrays(pairs):
+    chan, lag = (C.c_int32 * 64)(), (C.c_int32 * 64)()
+    for p, (c, l) in enumerate(pairs, start=1):
+        chan[p], lag[p] = c, l
+    return chan, lag
+
+
+def _gram_desc(pairs, T, N, Cc, Ty, L_in, H, first, step, count, pooled=False) -> TecmLinGram:
+    chan, lag = _pair_arrays(pairs)
+    return TecmLinGram(T=int(T), Ty=int(Ty), N=int(N), C=int(Cc), P=len(pairs) + 1, H=int(H), L_in=int(L_in), pooled=int(bool(pooled)),
+                       chan=chan, lag=lag, first=int(first), step=int(step), count=int(count))
+
+
+def linear_gram_geometry(pairs, T, N, Cc, Ty, L_in, H, first, step, count):
+    """(nodes per block, windows per staged chunk) of the `tecm_lin_gram` launch for this shape, asked of the library (pure
+    host arithmetic: no GPU needed); ValueError with the library's reason when the shape is not served."""
+    tile, chunk = C.c_int32(), C.c_int32()
+    desc = _gram_desc(pairs, T, N, Cc, Ty, L_in, H, first, step, count)
+    if not lib().tecm_lin_gram_supported(C.byref(desc), C.byref(tile), C.byref(chunk)):
+        raise ValueError(lib().tecm_last_error().decode("utf-8", "replace"))
+    return tile.value, chunk.value
+
+
+def linear_gram(X: torch.Tensor, ys: torch.Tensor, pairs, L_in: int, H: int, first: int, step: int, count: int, pooled: bool = False):
+    """The normal equations of every window a = first + i step, i < count: X (T, N, C) contiguous float32 and ys (Ty, N)
+    float32 of any non-negative strides, both on the device -> (gram (N, P, P+H) float64 = [G | R], gram_pooled (P, P+H) or
+    None).  One running fp64 sum per entry in ascending window order: the bits of a sequential host loop."""
+    require_gpu_tensor(X, "X")
+    require_gpu_tensor(ys, "ys")
+    if X.dim() != 3 or not X.is_contiguous():
+        raise ValueError(f"X must be a contiguous (T, N, C) tensor, got {tuple(X.shape)}")
+    T, N, Cc = X.shape
+    if ys.dim() != 2 or ys.shape[1] != N:
+        raise ValueError(f"ys must be (Ty, {N}), got {tuple(ys.shape)}")
+    desc = _gram_desc(pairs, T, N, Cc, ys.shape[0], L_in, H, first, step, count, pooled)
+    if not lib().tecm_lin_gram_supported(C.byref(desc), None, None):
+        raise ValueError(lib().tecm_last_error().decode("utf-8", "replace"))
+    P = len(pairs) + 1
+    gram = torch.empty(N, P, P + int(H), device=X.device, dtype=torch.float64)
+    gp = torch.empty(P, P + int(H), device=X.device, dtype=torch.float64) if pooled else None
+    desc.X, desc.ys, desc.ys_stride_t, desc.ys_stride_n = X.data_ptr(), ys.data_ptr(), ys.stride(0), ys.stride(1)
+    desc.gram, desc.gram_pooled = gram.data_ptr(), None if gp is None else gp.data_ptr()
+    check(lib().tecm_lin_gram(C.byref(desc), stream_ptr()), "tecm_lin_gram")
+    return gram, gp
+
+
+def linear_solve(gram: torch.Tensor, alpha: float):
+    """gram (N, P, P+H) float64 on the device -> (coef (N, P, H), coef_t (P, H, N), status (N) int32): the ridge solutions of
+    (G + alpha diag(0, 1, ..., 1)) W = R by Cholesky, `coef_t` the node-fastest copy the forecast reads."""
+    require_gpu_tensor(gram, "gram", torch.float64)
+    if gram.dim() != 3 or gram.shape[2] <= gram.shape[1] or not gram.is_contiguous():
+        raise ValueError(f"gram must be a contiguous (N, P, P + H) tensor, got {tuple(gram.shape)}")
+    N, P, H = gram.shape[0], gram.shape[1], gram.shape[2] - gram.shape[1]
+    coef = torch.empty(N, P, H, device=gram.device, dtype=torch.float64)
+    coef_t = torch.empty(P, H, N, device=gram.device, dtype=torch.float64)
+    status = torch.empty(N, device=gram.device, dtype=torch.int32)
+    s = TecmLinSolve(gram=gram.data_ptr(), N=N, P=P, H=H, alpha=float(alpha), coef=coef.data_ptr(), coef_t=coef_t.data_ptr(),
+                     status=status.data_ptr())
+    check(lib().tecm_lin_solve(C.byref(s), stream_ptr()), "tecm_lin_solve")
+    return coef, coef_t, status
+
+
+def rebuilt_target_series(Y: torch.Tensor) -> torch.Tensor:
+    """The target-scaled series behind a materialised Y (T, N, L_out), `Y[i, :, h] = Ys[i + 1 + h]`: (T + L_out, N) whose
+    rows 1 .. T are `Y[:, :, 0]` and whose last L_out - 1 rows are the last row's remaining horizons, in one
+    concatenation.  Row 0 is not in Y (no window's target reaches it) and is NaN."""
+    head = torch.full_like(Y[:1, :, 0], float("nan"))
+    return torch.cat([head, Y[:, :, 0], Y[-1, :, 1:].t()])
+
+
+def _progression(indices, num_samples: int):
+    """(first, step, count) of `indices` among a dataset's samples: None is every sample; else a range or a sequence that is
+    one (ascending, constant difference)."""
+    if indices is None:
+        idx = range(num_samples)
+    else:
+        try:
+            idx = indices if isinstance(indices, range) else [int(i) for i in indices]
+        except (TypeError, ValueError):
+            raise ValueError(f"indices must be None or a range-like arithmetic progression, got {indices!r}")
+    if len(idx) == 0:
+        raise ValueError("fit() needs at least one window")
+    first, step = int(idx[0]), int(idx[1]) - int(idx[0]) if len(idx) > 1 else 1
+    if step < 1 or any(int(idx[i]) != first + i * step for i in range(len(idx))):
+        raise ValueError("indices must be None or a range-like arithmetic progression with a positive step")
+    if first < 0 or first + (len(idx) - 1) * step >= num_samples:
+        raise ValueError(f"indices leave the dataset's {num_samples} samples")
+    return first, step, len(idx)
+
+
+class LinearBaseline:
+    """A per-node (or, with `pooled`, one shared) ridge regression from the input window to the L_out targets, fitted on
+    the device against the target-scaled series (see the module docstring).  Predictors: the intercept, `lags` of
+    `channel` (None: the last min(L_in, 48) steps), then the `exog` (channel, lag) pairs; look-back 1 is the last input
+    step.  After `fit`, numpy only: `coef_` (N or 1, P, H) float64 with row 0 the intercept, `status_` (N or 1) int32 with
+    the bits `DEGENERATE` (a Cholesky pivot vanished: the intercept-only model, whose forecast is the mean training target)
+    and `NONFINITE` (a NaN / inf in the node's data: NaN coefficients), `pairs_` and `n_windows_`."""
+    DEGENERATE, NONFINITE = _lib.TECM_LIN_DEGENERATE, _lib.TECM_LIN_NONFINITE
+
+    def __init__(self, lags=None, channel: int = 0, exog=(), alpha: float = 1.0, pooled: bool = False,
+                 device: Union[str, torch.device] = "cuda"):
+        if not float(alpha) >= 0.0:
+            raise ValueError(f"alpha must not be negative, got {alpha!r}")
+        self.lags = None if lags is None else list(lags)
+        self.channel, self.exog = int(channel), list(exog)
+        linear_pairs(self.lags, self.channel, self.exog, LINEAR_DEFAULT_LAGS)          # refuse bad pairs now
+        self.alpha, self.pooled, self.device = float(alpha), bool(pooled), torch.device(device)
+        self.coef_ = self.status_ = self.pairs_ = self.n_windows_ = self.L_in_ = self.H_ = self.num_nodes_ = self.tail_ = None
+        self._coef_dev = None
+
+    # joblib / pickle: numpy only
+    def __getstate__(self):
+        state = {k: v for k, v in self.__dict__.items() if k != "_coef_dev"}
+        state["device"] = str(self.device)
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.device, self._coef_dev = torch.device(state["device"]), None
+
+    def fit_series(self, X: torch.Tensor, ys: torch.Tensor, L_in: int, L_out: int, first: int, step: int,
+                   count: int) -> "LinearBaseline":
+        """Fits on the windows a = first + i step, i < count, of X (T, N, C) and the target-scaled series ys (Ty, N), device
+        tensors both: inputs X[a : a + L_in], targets ys[a + L_in : a + L_in + L_out]."""
+        pairs = linear_pairs(self.lags, self.channel, self.exog, L_in)
+        log.info("Fitting the linear baseline (%d predictors, %d windows)...", len(pairs), count)
+        gram, gp = linear_gram(X, ys, pairs, L_in, L_out, first, step, count, self.pooled)
+        coef, coef_t, status = linear_solve(gp.unsqueeze(0) if self.pooled else gram, self.alpha)
+        self._coef_dev = coef_t.view(coef_t.shape[0], coef_t.shape[1]) if self.pooled else coef_t
+        self.coef_, self.status_ = coef.cpu().numpy(), status.cpu().numpy()
+        self.pairs_, self.n_windows_, self.L_in_, self.H_, self.num_nodes_ = pairs, int(count), int(L_in), int(L_out), X.shape[1]
+        self.tail_ = X[X.shape[0] - int(L_in):].cpu().numpy()
+        log.info("Linear baseline fitted: %d degenerate, %d non-finite.", int((self.status_ & 1 != 0).sum()),
+                 int((self.status_ & 2 != 0).sum()))
+        return self
+
+    def fit(self, dataset, indices=None) -> "LinearBaseline":
+        """Fits on every sample of a `SlidingWindowSamplerDataset` or `SeriesWindowDataset`, or on the samples `indices`:
+        a range, or a sequence that is an ascending arithmetic progression (anything else raises ValueError)."""
+        first, step, count = _progression(indices, dataset.num_samples)
+        T, Hh, W, Cc = dataset.X.shape
+        N = Hh * W
+        if "Ys" in dataset.__dict__:
+            ys = dataset.Ys.view(dataset.Ys.shape[0], N)
+        else:
+            ys = rebuilt_target_series(dataset.Y.view(dataset.Y.shape[0], N, dataset.Y.shape[3]))
+        return self.fit_series(dataset.X.view(T, N, Cc), ys, dataset.L_in, dataset.L_out, first * dataset.stride,
+                               step * dataset.stride, count)
+
+    def _coef_on(self, device) -> torch.Tensor:
+        if self.coef_ is None:
+            raise ValueError("LinearBaseline used before fit()")
+        if self._coef_dev is None or self._coef_dev.device != device:
+            c = torch.as_tensor(self.coef_)
+            self._coef_dev = (c[0] if self.pooled else c.permute(1, 2, 0)).contiguous().to(device)
+        return self._coef_dev
+
+    def forecast_series(self, X: torch.Tensor, starts: Sequence[int], L_in: int, L_out: int, out: torch.Tensor = None,
+                        coef: torch.Tensor = None, host_check: bool = True) -> torch.Tensor:
+        """Forecasts from the windows X[a : a + L_in], a in `starts`, of a (T, N, C) float32 device tensor: (B, L_out, N)
+        float32, or written into `out` (any strides).  `coef` on the device, float64, (P, H, N) node-fastest or (P, H) for
+        every node, replaces the fitted coefficients.  Without `host_check` a window outside [0, T - L_in] reaches the
+        kernel, which writes NaN."""
+        require_gpu_tensor(X, "X")
+        if X.dim() != 3 or not X.is_contiguous():
+            raise ValueError(f"X must be a contiguous (T, N, C) tensor, got {tuple(X.shape)}")
+        T, N, Cc = X.shape
+        if self.pairs_ is None:
+            raise ValueError("LinearBaseline used before fit()")
+        if int(L_out) != self.H_:
+            raise ValueError(f"fitted for {self.H_} horizons, asked for L_out = {L_out}")
+        P = len(self.pairs_) + 1
+        coef = self._coef_on(X.device) if coef is None else coef
+        require_gpu_tensor(coef, "coef", torch.float64)
+        if tuple(coef.shape) not in ((P, self.H_, N), (P, self.H_)) or not coef.is_contiguous():
+            raise ValueError(f"coefficients of shape {tuple(coef.shape)} do not fit {P} predictors x {self.H_} horizons x {N} nodes")
+        host = torch.tensor([int(a) for a in starts], dtype=torch.int64)
+        B = host.numel()
+        if B == 0:
+            raise ValueError("forecast_series() needs at least one window")
+        if out is None:
+            out = torch.empty(B, int(L_out), N, device=X.device, dtype=torch.float32)
+        require_gpu_tensor(out, "out")
+        if out.shape != (B, int(L_out), N):
+            raise ValueError(f"out must be {(B, int(L_out), N)}, got {tuple(out.shape)}")
+        dev_starts = host.to(X.device, non_blocking=True)
+        w = TecmWindowBaseline(X=X.data_ptr(), starts=dev_starts.data_ptr(), starts_host_check=host.data_ptr() if host_check else None,
+                               T=T, N=N, C=Cc, channel=0, L_in=int(L_in), L_out=int(L_out), B=B, mode=0, period=0,
+                               out=out.data_ptr(), o_stride_b=out.stride(0), o_stride_h=out.stride(1) if L_out > 1 else 1,
+                               o_stride_n=out.stride(2))
+        chan, lag = _pair_arrays(self.pairs_)
+        f = TecmLinForecast(w=w, coef=coef.data_ptr(), coef_stride_n=1 if coef.dim() == 3 else 0, P=P, chan=chan, lag=lag)
+        check(lib().tecm_lin_forecast(C.byref(f), stream_ptr()), "tecm_lin_forecast")
+        return out
+
+    def forecast_windows(self, dataset, indices: Sequence[int]) -> torch.Tensor:
+        """Forecasts for the windows `indices` of a dataset as a (B, L_out, N, 1) device tensor, the layout of the model's
+        output: one launch for any number of windows.  The dataset's L_out must equal the fitted one."""
+        if self.coef_ is None:
+            raise ValueError("LinearBaseline used before fit()")
+        if dataset.L_out != self.H_:
+            raise ValueError(f"fitted for {self.H_} horizons, the dataset has L_out = {dataset.L_out}")
+        idx = [int(i) for i in indices]
+        for i in idx:
+            if not 0 <= i < dataset.num_samples:
+                raise IndexError(f"Index {i} is out of bounds for a dataset of size {dataset.num_samples}")
+        T, Hh, W, Cc = dataset.X.shape
+        starts = [dataset.sample_indices[i] for i in idx]
+        return self.forecast_series(dataset.X.view(T, Hh * W, Cc), starts, dataset.L_in, dataset.L_out).unsqueeze(-1)
+
+    def predict(self, node_indices, steps: int) -> dict:
+        """{node: (steps,) float64}, steps <= the fitted L_out, for the nodes among `node_indices`: the forecast from the
+        end of the series the model was fitted on, whose last L_in rows are the window."""
+        if self.coef_ is None:
+            raise ValueError("LinearBaseline.predict() before fit()")
+        if not 1 <= int(steps) <= self.H_:
+            raise ValueError(f"fitted for {self.H_} horizons, asked for {steps} steps")
+        tail = torch.as_tensor(self.tail_).to(self.device).contiguous()
+        out = self.forecast_series(tail, [0], self.L_in_, self.H_).cpu().numpy().astype(np.float64)
+        return {int(n): out[0, :int(steps), int(n)] for n in node_indices if 0 <= int(n) < self.num_nodes_}
 
 
 def save_baseline(model, path):

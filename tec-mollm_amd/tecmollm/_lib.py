@@ -267,6 +267,36 @@ class TecmSarForecast(C.Structure):
     ]
 
 
+class TecmLinGram(C.Structure):
+    _fields_ = [
+        ("X", c_f32p), ("T", C.c_int64),
+        ("ys", c_f32p), ("ys_stride_t", C.c_int64), ("ys_stride_n", C.c_int64), ("Ty", C.c_int64),
+        ("N", C.c_int32), ("C", C.c_int32), ("P", C.c_int32), ("H", C.c_int32), ("L_in", C.c_int32), ("pooled", C.c_int32),
+        ("chan", C.c_int32 * 64), ("lag", C.c_int32 * 64),
+        ("first", C.c_int64), ("step", C.c_int64), ("count", C.c_int64),
+        ("gram", C.c_void_p), ("gram_pooled", C.c_void_p),
+    ]
+
+
+class TecmLinSolve(C.Structure):
+    _fields_ = [
+        ("gram", C.c_void_p),
+        ("N", C.c_int32), ("P", C.c_int32), ("H", C.c_int32), ("_pad", C.c_int32),
+        ("alpha", C.c_double),
+        ("coef", C.c_void_p), ("coef_t", C.c_void_p),
+        ("status", C.c_void_p),
+    ]
+
+
+class TecmLinForecast(C.Structure):
+    _fields_ = [
+        ("w", TecmWindowBaseline),
+        ("coef", C.c_void_p), ("coef_stride_n", C.c_int64),
+        ("P", C.c_int32), ("_pad", C.c_int32),
+        ("chan", C.c_int32 * 64), ("lag", C.c_int32 * 64),
+    ]
+
+
 class TecmMoments(C.Structure):
     _fields_ = [
         ("src", C.c_void_p), ("rows", C.c_int64), ("cols", C.c_int64), ("ld", C.c_int64),
@@ -330,6 +360,8 @@ TECM_TATT_COUNT = 8
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
 TECM_SAR_MAX_K, TECM_SAR_MAX_LAG, TECM_SAR_MAX_LONG_AR, TECM_SAR_MAX_OFFSET, TECM_SAR_CHUNK = 12, 32, 64, 64, 1024
 TECM_SAR_DEGENERATE, TECM_SAR_NONFINITE, TECM_SAR_MA_DROPPED = 1, 2, 4
+TECM_LIN_MAX_P, TECM_LIN_MAX_H, TECM_LIN_MAX_LAG, TECM_LIN_MAX_CHANNELS = 64, 32, 512, 8
+TECM_LIN_DEGENERATE, TECM_LIN_NONFINITE = 1, 2
 TECM_MOMENTS_MAX_BLOCKS = 2048
 TECM_FEATURES_MAX_CI = 15
 
@@ -442,6 +474,10 @@ EXPORTS = {
     "tecm_sar_fit": (C.c_int, [C.POINTER(TecmSarFit), C.c_void_p]),
     "tecm_sar_solve": (C.c_int, [C.POINTER(TecmSarFit), C.c_void_p]),
     "tecm_sar_forecast": (C.c_int, [C.POINTER(TecmSarForecast), C.c_void_p]),
+    "tecm_lin_gram_supported": (C.c_int, [C.POINTER(TecmLinGram), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "tecm_lin_gram": (C.c_int, [C.POINTER(TecmLinGram), C.c_void_p]),
+    "tecm_lin_solve": (C.c_int, [C.POINTER(TecmLinSolve), C.c_void_p]),
+    "tecm_lin_forecast": (C.c_int, [C.POINTER(TecmLinForecast), C.c_void_p]),
     "tecm_moments_ws_bytes": (C.c_int64, [C.POINTER(TecmMoments)]),
     "tecm_moments": (C.c_int, [C.POINTER(TecmMoments), C.c_void_p]),
     "tecm_features_build": (C.c_int, [C.POINTER(TecmFeaturesBuild), C.c_void_p]),

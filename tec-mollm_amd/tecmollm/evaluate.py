@@ -36,19 +36,22 @@ KINDS = {"mean": _lib.TECM_BASELINE_MEAN, "last": _lib.TECM_BASELINE_LAST, "peri
 NAMES = {"mean": "HistoricalAverage", "last": "Persistence", "periodic": "DayAgo"}
 MODEL_NAME = "TEC-MoLLM"
 SARIMA_NAME = "SARIMA"      # a fitted src.models.baselines.SarimaBaseline given as an element of `baselines=`
+LINEAR_NAME = "Linear"      # a fitted src.models.baselines.LinearBaseline, likewise
 
 
 def baseline_name(kind) -> str:
-    """The result-dict name of one element of `baselines=`: a kind string of `KINDS`, or a fitted `SarimaBaseline`."""
+    """The result-dict name of one element of `baselines=`: a kind string of `KINDS`, or a fitted `SarimaBaseline` or
+    `LinearBaseline`."""
     if isinstance(kind, str):
         if kind in KINDS:
             return NAMES[kind]
     else:
-        from src.models.baselines import SarimaBaseline
-        if isinstance(kind, SarimaBaseline):
-            if kind.coef_ is None:
-                raise ValueError("a SarimaBaseline given as a baseline must be fitted")
-            return SARIMA_NAME
+        from src.models.baselines import LinearBaseline, SarimaBaseline
+        for cls, name in ((SarimaBaseline, SARIMA_NAME), (LinearBaseline, LINEAR_NAME)):
+            if isinstance(kind, cls):
+                if kind.coef_ is None:
+                    raise ValueError(f"a {cls.__name__} given as a baseline must be fitted")
+                return name
     raise ValueError(f"baselines must come from {sorted(KINDS)}, got {kind!r}")
 
 
@@ -158,8 +161,8 @@ def evaluate_split(model: torch.nn.Module, dataset, edge_index: torch.Tensor, ba
 
     One pass over the batches: the model's output and each baseline's stride-0 view are fed in place to a
     `HorizonMetrics` of their own, with no host synchronisation per batch.  An element of `baselines` is a kind string of
-    `window_baseline` or a fitted `src.models.baselines.SarimaBaseline`, whose entry is named "SARIMA" (one
-    `tecm_sar_forecast` launch per batch); the same holds for `evaluate_maps` and `evaluate_ensemble`.  `order` and `group` as in `loop.validate`:
+    `window_baseline`, a fitted `src.models.baselines.SarimaBaseline`, whose entry is named "SARIMA" (one
+    `tecm_sar_forecast` launch per batch), or a fitted `LinearBaseline`, named "Linear" (one `tecm_lin_forecast` launch); the same holds for `evaluate_maps` and `evaluate_ensemble`.  `order` and `group` as in `loop.validate`:
     a rank evaluates its shard and every rank returns the metrics of the whole split."""
     hms, _ = _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_weight, order, None, None)
     if not hms:

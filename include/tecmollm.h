@@ -531,6 +531,16 @@ int tecm_colsum_twin(const float* in, int64_t ld, int64_t outer, int64_t inner, 
  * backwards' (num_blocks, 2*D) partials, D = 768), else matrix by matrix.  in / out: HOST arrays of device pointers. */
 int tecm_colsum_batch(const float* const* in, float* const* out, int32_t nbuf, int64_t ld, int64_t rows, int32_t C,
                       float* workspace /* >= max(1024, 256*nbuf) * C floats */, void* stream);
+/* The route tecm_colsum (nbuf == 0) or tecm_colsum_batch (nbuf > 0 matrices of `outer` rows; inner = nseg = 1) takes for these
+ * arguments, from the plan function the launchers route by: "v4 rb=1024 chunk=17 waves=16" -- first stage (scalar: a lane per
+ * column; v4: a thread per row slot and column quad; batch: the scalar stage over a pointer table), partial rows per
+ * segment, input rows per partial row, waves per 64 columns of the second stage.  A batch answers "batch rb=.. chunk=..
+ * waves=.. launches=N" for its own pair(s) of launches (32 matrices a pair) and "each v4 ..." where every matrix goes through
+ * tecm_colsum one by one.  "" where the launcher refuses.  in_misalign_bytes: distance of the input from a 16-byte boundary
+ * (batch: of its best aligned matrix, which decides for all); the workspace is taken to be 16-byte aligned.  The environment
+ * switch TECM_COLSUM_MINROWS is included.  Pure host function; the string lives until this thread's next call. */
+const char* tecm_colsum_path(int64_t ld, int64_t outer, int64_t inner, int32_t nseg, int32_t C, int32_t in_misalign_bytes,
+                             int32_t nbuf);
 
 /* nn.HuberLoss(delta) mean (train.py:372) fused with its gradient: pred/target/dpred are (n) floats
  * addressed through pred_index: element e of pred = pred[e], target likewise (both contiguous in the
@@ -687,6 +697,9 @@ int tecm_pack_vectors(const float* const* srcs, const int32_t* lens, int32_t cou
  *   norm   = ||g||_2 over all n values ; coef = min(1, max_norm / (norm + 1e-6))   (max_norm <= 0: coef = 1)
  *   g     *= coef ; p *= 1 - lr*wd ; m = b1*m + (1-b1)*g ; v = b2*v + (1-b2)*g*g
  *   p     -= (lr / (1-b1^step)) * m / (sqrt(v)/sqrt(1-b2^step) + eps)
+ * A NaN norm gives a NaN coef (torch's clamp(max=1) keeps it): every parameter becomes NaN, as after the reference's step.
+ * 1 - beta and the bias corrections are formed in double from the decimal of at most six digits that rounds to the fp32
+ * beta handed over (0.999f -> 0.001, not 1.0f - 0.999f = 0.00099998713), as torch forms them from its Python floats.
  * total_norm_out[0] = norm (device scalar, optional).  zero_grad != 0 clears grad in the same pass
  * (optimizer.zero_grad(), train.py:105).  partials: >= TECM_NORM_BLOCKS doubles of workspace. */
 #define TECM_NORM_BLOCKS 512

@@ -176,11 +176,53 @@ __global__ __launch_bounds__(64 * WAVES) void colsum_stage2_batch(ColsumBatch ta
   colsum_stage2_body<WAVES>(ws + (int64_t)z * RB * C, RB, C, tab.out[z], C, 0, 1.0f, 0);
 }
 void launch_colsum_stage2(const float* ws, int RB, int nseg, int C, float* out, int64_t ldo, int accumulate, float scale,
-                          int colblocks, hipStream_t st) {
-  if (colblocks * nseg <= 4 && RB > 256)
+                          int colblocks, int waves, hipStream_t st) {
+  if (waves == 16)
     hipLaunchKernelGGL(colsum_stage2<16>, dim3(colblocks, nseg), dim3(1024), 0, st, ws, RB, nseg, C, out, ldo, accumulate, scale);
   else
     hipLaunchKernelGGL(colsum_stage2<8>, dim3(colblocks, nseg), dim3(512), 0, st, ws, RB, nseg, C, out, ldo, accumulate, scale);
+}
+
+// ------------------------------------------------------------------------------ routing: which kernels serve a call
+// Decided here and nowhere else: tecm_colsum / tecm_colsum_twin, tecm_colsum_batch and tecm_colsum_path all ask colsum_plan.
+// CS_SCALAR: colsum_stage1 (lane = column); CS_V4: colsum_stage1_v4 (thread = row slot x column quad); CS_BATCH:
+// colsum_stage1_batch (CS_SCALAR's blocks and chunks per matrix, a grid dimension walks the pointer table)
+enum ColsumStage1 { CS_NONE, CS_SCALAR, CS_V4, CS_BATCH };
+struct ColsumPlan {
+  ColsumStage1 stage1 = CS_NONE;                 // CS_NONE: refused
+  int colblocks = 0;                             // 64-column blocks of the second stage (and of CS_SCALAR / CS_BATCH)
+  int64_t rb = 0, chunk = 0;                     // partial rows per segment, rows of the input per partial row
+  int waves = 0;                                 // WAVES of colsum_stage2 / colsum_stage2_batch
+};
+// does the float4 first stage serve the matrix?  (in16: the input AND the workspace are 16-byte aligned)
+bool colsum_v4_ok(int64_t ld, int C, bool in16) { return C % 4 == 0 && C <= 1024 && ld % 4 == 0 && in16; }
+// total = outer * inner rows per segment; batch: the plan of tecm_colsum_batch's own pair of launches (nseg = 1)
+ColsumPlan colsum_plan(int64_t ld, int64_t total, int nseg, int C, bool in16, bool batch) {
+  ColsumPlan p;
+  if (!(total > 0 && nseg > 0 && C > 0)) return p;
+  p.colblocks = (C + 63) / 64;
+  if (!batch && colsum_v4_ok(ld, C, in16)) {
+    int64_t rb4 = 1024 / nseg;                          // workspace contract: >= 1024 * nseg * C floats
+    // at least 16 rows per block.  (Fewer, larger blocks to shrink the second stage were measured at B = 2 -- where the two
+    // stages of the 17 column sums are 0.35 ms of a 5.2 ms step: 512 rows per block 5.20 -> 5.85 ms, 2048 -> 7.9 ms, 16 instead
+    // of 64 -0.03 ms: the first stage lives on its block count.)  TECM_COLSUM_MINROWS overrides (diagnostics).
+    static const int64_t min_rows = [] { const char* e = std::getenv("TECM_COLSUM_MINROWS"); return e ? std::atoll(e) : 16ll; }();
+    if (rb4 > (total + min_rows - 1) / min_rows) rb4 = (total + min_rows - 1) / min_rows;
+    if (rb4 < 1) rb4 = 1;
+    p.chunk = (total + rb4 - 1) / rb4;
+    p.rb = (total + p.chunk - 1) / p.chunk;
+    p.stage1 = CS_V4;
+  } else {
+    int64_t rb = 1024 / ((int64_t)p.colblocks * nseg);
+    if (rb > 256) rb = 256;
+    if (rb > (total + 15) / 16) rb = (total + 15) / 16;
+    if (rb < 1) rb = 1;
+    p.chunk = (total + rb - 1) / rb;
+    p.rb = (total + p.chunk - 1) / p.chunk;
+    p.stage1 = batch ? CS_BATCH : CS_SCALAR;
+  }
+  p.waves = p.colblocks * nseg <= 4 && p.rb > 256 ? 16 : 8;
+  return p;
 }
 
 }  // namespace
@@ -190,40 +232,55 @@ static int colsum_impl(const float* in, int64_t ld, int64_t outer, int64_t inner
                        int64_t ld_twin, void* stream) {
   TECM_REQUIRE(in && out && workspace, TECM_E_ARG, "tecm_colsum: null pointer");
   TECM_REQUIRE(outer > 0 && inner > 0 && nseg > 0 && C > 0, TECM_E_ARG, "tecm_colsum: bad shape");
-  const int colblocks = (C + 63) / 64;
-  const int64_t total = outer * inner;
-  int64_t rb = 1024 / ((int64_t)colblocks * nseg);
-  if (rb > 256) rb = 256;
-  if (rb > (total + 15) / 16) rb = (total + 15) / 16;
-  if (rb < 1) rb = 1;
-  const int64_t chunk = (total + rb - 1) / rb;
-  rb = (total + chunk - 1) / chunk;
+  const ColsumPlan p = colsum_plan(ld, outer * inner, nseg, C, tecm_aligned(in, 16) && tecm_aligned(workspace, 16), false);
   hipStream_t st = (hipStream_t)stream;
   const DropCtxN idc = make_dropn(in_drop);
-  if (C % 4 == 0 && C <= 1024 && ld % 4 == 0 && tecm_aligned(in, 16) && tecm_aligned(workspace, 16)) {
-    int64_t rb4 = 1024 / nseg;                          // workspace contract: >= 1024 * nseg * C floats
-    // at least 16 rows per block.  (Fewer, larger blocks to shrink the second stage were measured at B = 2 -- where the two
-    // stages of the 17 column sums are 0.35 ms of a 5.2 ms step: 512 rows per block 5.20 -> 5.85 ms, 2048 -> 7.9 ms, 16 instead
-    // of 64 -0.03 ms: the first stage lives on its block count.)  TECM_COLSUM_MINROWS overrides (diagnostics).
-    static const int64_t min_rows = [] { const char* e = std::getenv("TECM_COLSUM_MINROWS"); return e ? std::atoll(e) : 16ll; }();
-    if (rb4 > (total + min_rows - 1) / min_rows) rb4 = (total + min_rows - 1) / min_rows;
-    if (rb4 < 1) rb4 = 1;
-    const int64_t chunk4 = (total + rb4 - 1) / rb4;
-    rb4 = (total + chunk4 - 1) / chunk4;
-    hipLaunchKernelGGL(colsum_stage1_v4, dim3((unsigned)rb4, nseg), dim3(256), 0, st, in, ld, outer, inner, nseg, C,
-                       idc, workspace, chunk4, static_cast<__bf16*>(twin), ld_twin);
+  if (p.stage1 == CS_V4) {
+    hipLaunchKernelGGL(colsum_stage1_v4, dim3((unsigned)p.rb, nseg), dim3(256), 0, st, in, ld, outer, inner, nseg, C,
+                       idc, workspace, p.chunk, static_cast<__bf16*>(twin), ld_twin);
     TECM_CHECK_LAUNCH("tecm_colsum/stage1_v4");
-    launch_colsum_stage2(workspace, (int)rb4, nseg, C, out, ldo, accumulate, scale, colblocks, st);
+    launch_colsum_stage2(workspace, (int)p.rb, nseg, C, out, ldo, accumulate, scale, p.colblocks, p.waves, st);
     TECM_CHECK_LAUNCH("tecm_colsum/stage2");
     return TECM_OK;
   }
   TECM_REQUIRE(!twin, TECM_E_ALIGN, "tecm_colsum_twin: needs C %% 4 == 0, C <= 1024 and 16-byte friendly rows");
-  hipLaunchKernelGGL(colsum_stage1, dim3(colblocks, (unsigned)rb, nseg), dim3(256), 0, st, in, ld, outer, inner, nseg,
-                     C, idc, workspace, chunk);
+  hipLaunchKernelGGL(colsum_stage1, dim3(p.colblocks, (unsigned)p.rb, nseg), dim3(256), 0, st, in, ld, outer, inner, nseg,
+                     C, idc, workspace, p.chunk);
   TECM_CHECK_LAUNCH("tecm_colsum/stage1");
-  launch_colsum_stage2(workspace, (int)rb, nseg, C, out, ldo, accumulate, scale, colblocks, st);
+  launch_colsum_stage2(workspace, (int)p.rb, nseg, C, out, ldo, accumulate, scale, p.colblocks, p.waves, st);
   TECM_CHECK_LAUNCH("tecm_colsum/stage2");
   return TECM_OK;
+}
+
+// The route of a call without launching it: "v4 rb=1024 chunk=17 waves=16" -- first stage (scalar: colsum_stage1, v4:
+// colsum_stage1_v4, batch: colsum_stage1_batch), partial rows per segment, input rows per partial row, WAVES of the second
+// stage; "" where the launcher refuses.  nbuf == 0: tecm_colsum; nbuf > 0: tecm_colsum_batch of nbuf matrices (outer rows,
+// inner = nseg = 1), "batch ... launches=2" for its own pair(s) of launches, "each v4 ..." where every matrix goes through
+// tecm_colsum one by one.  in_misalign_bytes: distance of the input from a 16-byte boundary (batch: of its best aligned
+// matrix, which decides for all); the workspace is taken to be aligned.  Pure host function; the string lives until this
+// thread's next call.
+extern "C" const char* tecm_colsum_path(int64_t ld, int64_t outer, int64_t inner, int32_t nseg, int32_t C,
+                                        int32_t in_misalign_bytes, int32_t nbuf) {
+  static thread_local char buf[96];
+  static const char* const names[] = {"", "scalar", "v4", "batch"};
+  buf[0] = 0;
+  if (!(outer > 0 && inner > 0 && nseg > 0 && C > 0 && nbuf >= 0)) return buf;
+  const bool in16 = in_misalign_bytes % 16 == 0;
+  if (nbuf == 0) {
+    const ColsumPlan p = colsum_plan(ld, outer * inner, nseg, C, in16, false);
+    std::snprintf(buf, sizeof buf, "%s rb=%lld chunk=%lld waves=%d", names[p.stage1], (long long)p.rb, (long long)p.chunk, p.waves);
+    return buf;
+  }
+  if (inner != 1 || nseg != 1 || ld < C) return buf;
+  if (colsum_v4_ok(ld, C, in16)) {
+    const ColsumPlan p = colsum_plan(ld, outer, 1, C, true, false);
+    std::snprintf(buf, sizeof buf, "each %s rb=%lld chunk=%lld waves=%d", names[p.stage1], (long long)p.rb, (long long)p.chunk, p.waves);
+    return buf;
+  }
+  const ColsumPlan p = colsum_plan(ld, outer, 1, C, false, true);
+  std::snprintf(buf, sizeof buf, "%s rb=%lld chunk=%lld waves=%d launches=%d", names[p.stage1], (long long)p.rb, (long long)p.chunk,
+                p.waves, (nbuf + COLSUM_BATCH_MAX - 1) / COLSUM_BATCH_MAX);
+  return buf;
 }
 
 extern "C" int tecm_colsum(const float* in, int64_t ld, int64_t outer, int64_t inner, int32_t nseg, int32_t C,
@@ -250,10 +307,8 @@ extern "C" int tecm_colsum_batch(const float* const* in, float* const* out, int3
                                  float* workspace, void* stream) {
   TECM_REQUIRE(in && out && workspace && nbuf > 0 && rows > 0 && C > 0 && ld >= C, TECM_E_ARG, "tecm_colsum_batch: bad arguments");
   for (int i = 0; i < nbuf; ++i) TECM_REQUIRE(in[i] && out[i], TECM_E_ARG, "tecm_colsum_batch: null matrix %d", i);
-  const int colblocks = (C + 63) / 64;
   bool any4 = false;                // would tecm_colsum take its float4 first stage for one of the matrices?
-  if (C % 4 == 0 && C <= 1024 && ld % 4 == 0 && tecm_aligned(workspace, 16))
-    for (int i = 0; i < nbuf; ++i) any4 = any4 || tecm_aligned(in[i], 16);
+  for (int i = 0; i < nbuf; ++i) any4 = any4 || colsum_v4_ok(ld, C, tecm_aligned(in[i], 16) && tecm_aligned(workspace, 16));
   if (any4) {                       // then every matrix goes through tecm_colsum's own choice, one by one
     for (int i = 0; i < nbuf; ++i) {
       const int rc = colsum_impl(in[i], ld, rows, 1, 1, C, out[i], C, 0, 1.0f, nullptr, workspace, nullptr, 0, stream);
@@ -261,24 +316,19 @@ extern "C" int tecm_colsum_batch(const float* const* in, float* const* out, int3
     }
     return TECM_OK;
   }
-  int64_t rb = 1024 / (int64_t)colblocks;               // as colsum_impl with nseg = 1
-  if (rb > 256) rb = 256;
-  if (rb > (rows + 15) / 16) rb = (rows + 15) / 16;
-  if (rb < 1) rb = 1;
-  const int64_t chunk = (rows + rb - 1) / rb;
-  rb = (rows + chunk - 1) / chunk;
+  const ColsumPlan p = colsum_plan(ld, rows, 1, C, false, true);       // as tecm_colsum's lane-per-column route with nseg = 1
   hipStream_t st = (hipStream_t)stream;
   for (int i0 = 0; i0 < nbuf; i0 += COLSUM_BATCH_MAX) {
     const int n = nbuf - i0 < COLSUM_BATCH_MAX ? nbuf - i0 : COLSUM_BATCH_MAX;
     ColsumBatch tab{};
     for (int i = 0; i < n; ++i) { tab.in[i] = in[i0 + i]; tab.out[i] = out[i0 + i]; }
-    float* ws = workspace + (int64_t)i0 * rb * C;
-    hipLaunchKernelGGL(colsum_stage1_batch, dim3(colblocks, (unsigned)rb, n), dim3(256), 0, st, tab, ld, rows, C, ws, chunk);
+    float* ws = workspace + (int64_t)i0 * p.rb * C;
+    hipLaunchKernelGGL(colsum_stage1_batch, dim3(p.colblocks, (unsigned)p.rb, n), dim3(256), 0, st, tab, ld, rows, C, ws, p.chunk);
     TECM_CHECK_LAUNCH("tecm_colsum_batch/stage1");
-    if (colblocks <= 4 && rb > 256)
-      hipLaunchKernelGGL(colsum_stage2_batch<16>, dim3(colblocks, n), dim3(1024), 0, st, tab, ws, (int)rb, C);
+    if (p.waves == 16)
+      hipLaunchKernelGGL(colsum_stage2_batch<16>, dim3(p.colblocks, n), dim3(1024), 0, st, tab, ws, (int)p.rb, C);
     else
-      hipLaunchKernelGGL(colsum_stage2_batch<8>, dim3(colblocks, n), dim3(512), 0, st, tab, ws, (int)rb, C);
+      hipLaunchKernelGGL(colsum_stage2_batch<8>, dim3(p.colblocks, n), dim3(512), 0, st, tab, ws, (int)p.rb, C);
     TECM_CHECK_LAUNCH("tecm_colsum_batch/stage2");
   }
   return TECM_OK;

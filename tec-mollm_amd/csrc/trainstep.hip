@@ -1,6 +1,9 @@
 // The shell around the model step: fused global-norm clip + AdamW on flat
 // buffers (train.py:92-109, :358-366), evaluation statistics on device (src/evaluation/metrics.py),
 // sliding-window batch assembly (src/data/dataset.py:65-99).  All three are HBM-bound streaming kernels.
+#include <cstdio>
+#include <cstdlib>
+
 #include "common.h"
 #include "metrics_value.h"
 
@@ -55,7 +58,10 @@ __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, float
   acc = block_sum_f64(acc, red);
   const float norm = (float)sqrt(acc) * fabsf(grad_scale);
   float coef = 1.0f;
-  if (max_norm > 0.f) coef = fminf(max_norm / (norm + 1e-6f), 1.0f);
+  if (max_norm > 0.f) {                       // clamp(max = 1) as torch's clip_grad_norm_ does it: a NaN norm gives a NaN coefficient
+    const float r = max_norm / (norm + 1e-6f);  // (fminf would return 1 and let the step go on with the finite gradients)
+    coef = r >= 1.0f ? 1.0f : r;
+  }
   if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = norm;
   const float gs = grad_scale * coef;
 
@@ -197,6 +203,17 @@ extern "C" int tecm_checksum_verify(const float* tail, int32_t world, int32_t* e
   return TECM_OK;
 }
 
+// beta as the caller wrote it.  The descriptor carries fp32, so 0.999 arrives as 0.99900001287 and 1.0f - beta would be
+// 0.00099998713: 1.3e-5 off the 0.001 torch.optim.AdamW multiplies g * g by (it forms 1 - beta2 in double), in every increment
+// of exp_avg_sq and in the bias correction.  Where a decimal of at most six digits rounds to exactly this float, that decimal
+// is what was meant; any other float is taken as it is.
+static double beta_as_written(float beta) {
+  char buf[32];
+  std::snprintf(buf, sizeof buf, "%.6g", (double)beta);
+  const double d = std::strtod(buf, nullptr);
+  return (float)d == beta ? d : (double)beta;
+}
+
 extern "C" int tecm_adamw_clip_step(const TecmAdamW* a, void* stream) {
   TECM_REQUIRE(a, TECM_E_ARG, "tecm_adamw_clip_step: null descriptor");
   TECM_REQUIRE(a->param && a->grad && a->exp_avg && a->exp_avg_sq && a->partials, TECM_E_ARG,
@@ -213,10 +230,11 @@ extern "C" int tecm_adamw_clip_step(const TecmAdamW* a, void* stream) {
   hipLaunchKernelGGL(sumsq_kernel, dim3(nb), dim3(256), 0, st, a->grad, a->n, a->partials);
   TECM_CHECK_LAUNCH("tecm_adamw_clip_step/sumsq");
   AdamConsts c;
-  const double bc1 = 1.0 - pow((double)a->beta1, (double)a->step);
-  const double bc2 = 1.0 - pow((double)a->beta2, (double)a->step);
+  const double b1 = beta_as_written(a->beta1), b2 = beta_as_written(a->beta2);
+  const double bc1 = 1.0 - pow(b1, (double)a->step);
+  const double bc2 = 1.0 - pow(b2, (double)a->step);
   c.decay = 1.0f - a->lr * a->weight_decay;
-  c.b1 = a->beta1; c.b2 = a->beta2; c.omb1 = 1.0f - a->beta1; c.omb2 = 1.0f - a->beta2;
+  c.b1 = a->beta1; c.b2 = a->beta2; c.omb1 = (float)(1.0 - b1); c.omb2 = (float)(1.0 - b2);
   c.step_size = (float)((double)a->lr / bc1);
   c.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   c.eps = a->eps;

@@ -539,6 +539,14 @@ def colsum(inp: torch.Tensor, ld: int, outer: int, inner: int, nseg: int, Cn: in
     return out
 
 
+def colsum_path(ld: int, outer: int, inner: int, nseg: int, Cn: int, in_misalign_bytes: int = 0, nbuf: int = 0) -> str:
+    """The route colsum (nbuf = 0) or colsum_batch (nbuf matrices of `outer` rows) takes -- "v4 rb=1024 chunk=17 waves=16":
+    first stage, partial rows per segment, input rows per partial row, waves of the second stage; a batch answers
+    "batch ... launches=N" or, where every matrix goes through colsum one by one, "each v4 ..."; "" where the library
+    refuses.  in_misalign_bytes: of the input (batch: of its best aligned matrix).  Pure host arithmetic."""
+    return lib().tecm_colsum_path(ld, outer, inner, nseg, Cn, in_misalign_bytes, nbuf).decode()
+
+
 def colsum_batch(mats: List[torch.Tensor], rows: int, Cn: int) -> torch.Tensor:
     """(len(mats), Cn): row i = the column sums of the contiguous (rows, Cn) fp32 matrix mats[i] -- what
     colsum(mats[i], Cn, rows, 1, 1, Cn) returns, bit for bit -- from one native call for all of them."""

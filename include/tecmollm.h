@@ -961,6 +961,88 @@ typedef struct {
 } TecmBlockBootstrap;
 int tecm_block_bootstrap(const TecmBlockBootstrap* b, void* stream);
 
+/* (3j) event verification: did the forecast announce the event?  Integer counts only, so every order of additions gives the
+ * same bits and the tests compare with no tolerance.
+ *
+ * Value pipeline: the forecast (or every member) and the truth go through the value pipeline of (3) / (3b) (non-finite scaled
+ * prediction -> 0, inverse transform with two f32 roundings, nan_to_num, optional clip of the prediction only), which leaves
+ * float32 p (or x_1..x_K) and y in TECU.
+ * Threshold: t = thr[q*th_stride_q + slot*th_stride_k + i*th_stride_i], float32 on the device, in TECU.  Any stride may be 0:
+ * an absolute threshold is one float with all strides 0, a climatology-relative one a (Q, 12, N) table.  slot = slot[s*H + h],
+ * an int32 (S, H) tensor on the device; NULL means slot 0 with num_slots = 1.  A slot id outside [0, num_slots) skips that
+ * (sample, horizon) in every cell and sets TECM_BAD_SLOT in *err_flag (never NULL, sticky); it is never clamped.
+ * Event of threshold q: v > t when dir[q] > 0, v < t when dir[q] < 0, compared in float32 and strictly: a value equal to the
+ * threshold is no event, and neither is anything against a NaN threshold.  dir is a host array in the descriptor, no entry 0;
+ * 1 <= Q <= TECM_EVENT_MAX_Q.
+ * Groups as in (3b): an id outside [0, G) skips the sample and sets TECM_BAD_GROUP; cells of a group that does not occur in
+ * the call are neither read nor written.
+ *
+ * (a) tecm_event_hist: K members addressed as in (3c) (base[k*m_stride_k + s*m_stride_s + h*m_stride_h + i*m_stride_i], read
+ *     in place, 1 <= K <= TECM_ENS_MAX_K; K = 1 with any m_stride_k is a deterministic forecast: the model's permuted view and
+ *     a stride-0 baseline view are read where they lie), the target as in (3b).  ACCUMULATED across samples and calls:
+ *       hist (G, Q, H, K+1, 2, I) uint32, ((((g*Q + q)*H + h)*(K+1) + j)*2 + e)*I + i, node-contiguous:
+ *         e = 0: the number of samples in which exactly j members forecast the event
+ *         e = 1: how many of those samples had the event in the truth
+ *     For K = 1 this IS the contingency table: o_1 hits, n_1 - o_1 false alarms, o_0 misses, n_0 - o_0 correct negatives.
+ *     One wave per (tile of 64 nodes, horizon, group): lanes run along the nodes, a thread owns every count of its cell
+ *     (g, ., h, ., ., i), loads its operands once per (sample, horizon, node) and compares them with all Q thresholds.  When
+ *     the (K+1)*2*Q words of a node are at most TECM_EVENT_LDS_WORDS the wave counts in a column of LDS per lane and adds to
+ *     `hist` once at the end; otherwise the thread reads, increments and writes the cells it owns in `hist`.  No atomics.
+ *     Limits: G and H <= 65535, scale != 0, all addressing 64-bit. */
+#define TECM_BAD_SLOT 128
+#define TECM_EVENT_MAX_Q 8
+#define TECM_EVENT_LDS_WORDS 256
+typedef struct {
+  const float* members; int64_t m_stride_k, m_stride_s, m_stride_h, m_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  int64_t S; int32_t H; int32_t G; int64_t I;          /* samples, horizons, groups, nodes */
+  int32_t K; int32_t Q;                                /* members, thresholds */
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  int32_t num_slots;
+  const float* thr; int64_t th_stride_q, th_stride_k, th_stride_i;
+  const int32_t* slot;
+  int32_t dir[TECM_EVENT_MAX_Q];
+  uint32_t* hist;
+  const int32_t* group;
+  int32_t* err_flag;
+} TecmEventHist;
+int tecm_event_hist(const TecmEventHist* e, void* stream);
+
+/* (b) tecm_event_fss: the sums of the fractions skill score (Roberts & Lean 2008) of a deterministic forecast on a
+ *     rows x cols grid, node i = r*cols + c, I == rows*cols.  Per (sample, horizon, threshold) Bf, Bo are the binary event
+ *     fields of forecast and truth and cf(x), co(x) their box sums over the n x n window centred on x, cells outside the grid
+ *     counting as no event (zero padding).  For W odd widths n_w (host array, 1 <= W <= TECM_EVENT_MAX_W, 1 <= n <= 127),
+ *     ACCUMULATED across samples and calls:
+ *       sums (G, Q, H, W, 3) uint64, (((g*Q + q)*H + h)*W + w)*3 + n:  [sum_x (cf - co)^2, sum_x cf^2, sum_x co^2]
+ *     The common 1 / n^4 cancels: FSS = 1 - sums[0] / (sums[1] + sums[2]) is formed on the host.
+ *     One block per (sample, horizon): the event bits of all Q thresholds of both fields are staged in LDS once (a byte per
+ *     node and field), then per threshold two summed-area tables are built there and the widths walked; a block adds its
+ *     3 W integer sums per threshold to `sums` with 64-bit integer atomic adds (integers: order-free, the same bits).
+ *     The largest grid follows from the LDS map (768 B of reduction space, 8 (rows+1) (cols+1) B of tables, 2 I B of bits, in
+ *     64 KiB) and is answered by tecm_event_fss_supported(rows, cols) (pure host, 1 = served); 41 x 71 takes 30.1 KiB.
+ *     Limits: S and H <= 65535, scale != 0. */
+#define TECM_EVENT_MAX_W 8
+typedef struct {
+  const float* pred; int64_t p_stride_s, p_stride_h, p_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  int64_t S; int32_t H; int32_t G; int64_t I;          /* samples, horizons, groups, nodes */
+  int32_t rows, cols;
+  int32_t Q; int32_t W;                                /* thresholds, widths */
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  int32_t num_slots;
+  const float* thr; int64_t th_stride_q, th_stride_k, th_stride_i;
+  const int32_t* slot;
+  int32_t dir[TECM_EVENT_MAX_Q];
+  int32_t widths[TECM_EVENT_MAX_W];
+  uint64_t* sums;
+  const int32_t* group;
+  int32_t* err_flag;
+} TecmEventFss;
+int tecm_event_fss(const TecmEventFss* e, void* stream);
+int tecm_event_fss_supported(int32_t rows, int32_t cols);
+
 /* (4) sliding-window batch assembly from device-resident series (SlidingWindowSamplerDataset.__getitem__
  * src/data/dataset.py:65-99 + the harness reshapes train.py:62-65, :76): for sample b with window
  * start a = starts[b] (already multiplied by the dataset stride):

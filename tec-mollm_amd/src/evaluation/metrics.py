@@ -10,7 +10,9 @@ from 8*L_out doubles in `compute()` -- the only device->host copy of the whole e
 `derive` turns statistics of any leading shape into the metrics, NaN where a cell saw no sample.  `EnsembleMetrics` scores a
 K-member ensemble per cell the same way (`tecm_ensemble_stats`: CRPS, spread, coverage, rank histogram; `derive_ensemble`).
 `IntervalMetrics` scores conformal prediction intervals per cell (`tecm_interval_stats`: coverage, side of the misses, width,
-Winkler score; `derive_intervals`); the intervals themselves come from `tecmollm/conformal.py`.
+Winkler score; `derive_intervals`); the intervals themselves come from `tecmollm/conformal.py`.  `EventMetrics` counts events
+per cell and threshold (`tecm_event_hist`, `tecm_event_fss`: contingency tables, the member histogram behind Brier / reliability
+/ ROC, the sums of the fractions skill score; `derive_events`, `derive_fss`); thresholds and the pass are in `tecmollm/events.py`.
 
 Same numbers as the reference: inverse StandardScaler transform, non-finite guards, clip of predictions
 to [0, 200] TECU, MAE / RMSE / R^2 (sklearn semantics) / Pearson r per horizon and their averages.
@@ -499,4 +501,229 @@ class IntervalMetrics:
         out: Dict[str, object] = dict(derive_intervals(st))
         out["nominal_coverage"] = self.nominal_coverage
         out["by_group"] = [_pooled_intervals(derive_intervals(st[g].sum(axis=1))) for g in range(self.G)]
+        return out
+
+
+# ------------------------------------------------------------------------------------ event verification
+EVENT_CATEGORICAL_KEYS = ("base_rate", "pod", "far", "pofd", "csi", "ets", "hss", "frequency_bias")
+EVENT_PROBABILISTIC_KEYS = ("brier", "brier_reliability", "brier_resolution", "brier_uncertainty", "brier_skill", "roc_area")
+EVENT_KEYS = EVENT_CATEGORICAL_KEYS + EVENT_PROBABILISTIC_KEYS
+EVENT_TABLE = ("hits", "false_alarms", "misses", "correct_negatives")
+
+
+def _categorical(a, b, c, d) -> Dict[str, np.ndarray]:
+    """The EVENT_CATEGORICAL_KEYS of float64 tables [hits a, false alarms b, misses c, correct negatives d] of any shape,
+    NaN where a denominator is 0: base_rate (a+c)/n, pod a/(a+c), far b/(a+b) (the false-alarm RATIO), pofd b/(b+d), csi
+    a/(a+b+c), ets (a-r)/(a+b+c-r) with r = (a+b)(a+c)/n, hss 2(ad-bc)/((a+c)(c+d)+(a+b)(b+d)), frequency_bias (a+b)/(a+c)."""
+    n = a + b + c + d
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = (a + b) * (a + c) / n
+        return {"base_rate": (a + c) / n, "pod": a / (a + c), "far": b / (a + b), "pofd": b / (b + d),
+                "csi": a / (a + b + c), "ets": (a - r) / (a + b + c - r),
+                "hss": 2.0 * (a * d - b * c) / ((a + c) * (c + d) + (a + b) * (b + d)),
+                "frequency_bias": (a + b) / (a + c)}
+
+
+def _probabilistic(n: np.ndarray, o: np.ndarray) -> Dict[str, np.ndarray]:
+    """Float64 counts n_j, o_j of shape (..., K+1) -> the EVENT_PROBABILISTIC_KEYS over the leading axes plus "roc_curve"
+    (..., K+2, 2) = (pofd, pod) from (0, 0) to (1, 1).  The forecast probability of count j is j / K."""
+    K = n.shape[-1] - 1
+    f = np.arange(K + 1, dtype=np.float64) / K
+    with np.errstate(divide="ignore", invalid="ignore"):
+        N = n.sum(axis=-1)
+        obar = o.sum(axis=-1) / N
+        bs = ((n - o) * f * f + o * (1.0 - f) * (1.0 - f)).sum(axis=-1) / N
+        oj = np.where(n > 0, o / np.where(n > 0, n, 1.0), 0.0)               # an empty bin adds nothing to either term
+        rel = (n * (f - oj) ** 2).sum(axis=-1) / N
+        res = (n * (oj - obar[..., None]) ** 2).sum(axis=-1) / N
+        unc = obar * (1.0 - obar)
+        skill = 1.0 - bs / unc
+        # "at least j members", j = K+1 (never), K, ..., 1, 0 (always)
+        ev, ne = o.sum(axis=-1, keepdims=True), (n - o).sum(axis=-1, keepdims=True)
+        zero = np.zeros(n.shape[:-1] + (1,))
+        hit = np.concatenate([zero, np.cumsum(o[..., ::-1], axis=-1)], axis=-1) / ev
+        fa = np.concatenate([zero, np.cumsum((n - o)[..., ::-1], axis=-1)], axis=-1) / ne
+        area = (0.5 * (hit[..., 1:] + hit[..., :-1]) * (fa[..., 1:] - fa[..., :-1])).sum(axis=-1)
+    return {"brier": bs, "brier_reliability": rel, "brier_resolution": res, "brier_uncertainty": unc, "brier_skill": skill,
+            "roc_area": area, "roc_curve": np.stack([fa, hit], axis=-1)}
+
+
+def derive_events(hist: np.ndarray) -> Dict[str, np.ndarray]:
+    """(G, Q, H, K+1, 2, N) integer counts of `tecm_event_hist` -- [..., j, 0, i] the samples in which exactly j members
+    forecast the event, [..., j, 1, i] those of them in which it occurred -- -> float64 scores, NaN where a denominator is 0:
+      "count" (G, Q, H, N), "table" (G, Q, H, 4, N) = EVENT_TABLE, where the forecast says yes when at least half the members
+      do (2 j >= K; for K = 1 the forecast itself: o_1 hits, n_1 - o_1 false alarms, o_0 misses, n_0 - o_0 correct negatives);
+      the EVENT_CATEGORICAL_KEYS as (G, Q, H, N), as "<key>_pooled" (G, Q, H) from the tables summed over the nodes and as
+      "<key>_all" (G, Q) from the tables summed over nodes and horizons (summed tables, not averaged ratios), with
+      "table_pooled" (G, Q, H, 4) and "table_all" (G, Q, 4);
+      for K > 1 the EVENT_PROBABILISTIC_KEYS in the same three forms -- Brier score, its reliability / resolution /
+      uncertainty terms (forecasts take the K + 1 values j / K, so BS = REL - RES + UNC holds exactly), the skill against
+      the sample's own base rate, the area under the ROC (trapezoid over the K + 2 points "at least j members", (0, 0) and
+      (1, 1) included) -- plus "reliability" (G, Q, H, K+1, 2) = (n_j, o_j / n_j) and "roc_curve" (G, Q, H, K+2, 2) = (pofd,
+      pod), both pooled over the nodes."""
+    hs = np.asarray(hist)
+    if hs.ndim != 6 or hs.shape[4] != 2 or not np.issubdtype(hs.dtype, np.integer):
+        raise ValueError(f"hist must be an integer (G, Q, H, K+1, 2, N) array, got {hs.dtype} {hs.shape}")
+    hs = hs.astype(np.int64)
+    K = hs.shape[3] - 1
+    n_j, o_j = hs[:, :, :, :, 0, :], hs[:, :, :, :, 1, :]                  # (G, Q, H, K+1, N)
+    yes = 2 * np.arange(K + 1) >= K
+    a, c = o_j[:, :, :, yes].sum(axis=3), o_j[:, :, :, ~yes].sum(axis=3)
+    b, d = n_j[:, :, :, yes].sum(axis=3) - a, n_j[:, :, :, ~yes].sum(axis=3) - c
+    table = np.stack([a, b, c, d], axis=3)                                 # (G, Q, H, 4, N) int64
+    out: Dict[str, np.ndarray] = {"count": n_j.sum(axis=3).astype(np.float64), "table": table.astype(np.float64)}
+    forms = (("", table), ("_pooled", table.sum(axis=4)), ("_all", table.sum(axis=(2, 4))))
+    for suffix, t in forms:
+        if suffix:
+            out["table" + suffix] = t.astype(np.float64)
+        axis = 3 if suffix != "_all" else 2
+        parts = [np.take(t, k, axis=axis).astype(np.float64) for k in range(4)]
+        for k, v in _categorical(*parts).items():
+            out[k + suffix] = v
+    if K > 1:
+        no = np.stack([n_j, o_j], axis=-1)                                 # (G, Q, H, K+1, N, 2)
+        per_node = np.moveaxis(no, 3, 4)                                   # (G, Q, H, N, K+1, 2)
+        pooled, everything = no.sum(axis=4), no.sum(axis=(2, 4))           # (G, Q, H, K+1, 2), (G, Q, K+1, 2)
+        for suffix, t in (("", per_node), ("_pooled", pooled), ("_all", everything)):
+            t = t.astype(np.float64)
+            prob = _probabilistic(t[..., 0], t[..., 1])
+            for k in EVENT_PROBABILISTIC_KEYS:
+                out[k + suffix] = prob[k]
+            if suffix == "_pooled":
+                out["roc_curve"] = prob["roc_curve"]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            n, o = pooled[..., 0].astype(np.float64), pooled[..., 1].astype(np.float64)
+            out["reliability"] = np.stack([n, o / n], axis=-1)
+    return out
+
+
+def derive_fss(sums: np.ndarray, base_rate: np.ndarray) -> Dict[str, np.ndarray]:
+    """(G, Q, H, W, 3) integer sums [sum (cf - co)^2, sum cf^2, sum co^2] of `tecm_event_fss` -> "fss" (G, Q, H, W) = 1 -
+    sums[0] / (sums[1] + sums[2]), NaN where neither field ever held an event; "fss_pooled" (G, Q, W) from the sums added over
+    the horizons; "fss_uniform" = 0.5 + f_o / 2 with f_o = `base_rate` (any shape): the score of a forecast as large as the
+    observed fraction everywhere, above which a scale counts as skilful (Roberts & Lean 2008)."""
+    sm = np.asarray(sums)
+    if sm.ndim != 5 or sm.shape[-1] != 3:
+        raise ValueError(f"sums must be (G, Q, H, W, 3), got {sm.shape}")
+    sm = sm.astype(np.float64)
+    tot = sm.sum(axis=2)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return {"fss": 1.0 - sm[..., 0] / (sm[..., 1] + sm[..., 2]),
+                "fss_pooled": 1.0 - tot[..., 0] / (tot[..., 1] + tot[..., 2]),
+                "fss_uniform": 0.5 + np.asarray(base_rate, dtype=np.float64) / 2.0}
+
+
+class EventMetrics:
+    """Event verification per cell (group of the sample, threshold, horizon, node): did the forecast announce that TEC would
+    cross a threshold?  `thresholds` is a `tecmollm.events.EventThresholds`.  update(pred_or_members, true, groups, slots) per
+    batch on the device (`tecm_event_hist`, and with `grid` = (rows, cols) `tecm_event_fss` over the window widths `scales`):
+    integer counts only, so the same batches in any order give the same bits.  members = 1 scores a deterministic forecast
+    (contingency scores, FSS), members = K > 1 an ensemble (Brier score and its decomposition, reliability, ROC), compute()
+    at the end."""
+
+    def __init__(self, num_horizons: int, num_nodes: int, thresholds, num_groups: int = 1, scaler=None, members: int = 1,
+                 grid=None, scales=(1, 3, 5, 9), device: Union[str, torch.device] = "cuda"):
+        self.H, self.I, self.G, self.K = int(num_horizons), int(num_nodes), int(num_groups), int(members)
+        if min(self.H, self.I, self.G) < 1:
+            raise ValueError("EventMetrics needs at least one horizon, one node and one group")
+        if not 1 <= self.K <= _lib.TECM_ENS_MAX_K:
+            raise ValueError(f"members must lie in [1, {_lib.TECM_ENS_MAX_K}], got {self.K}")
+        self.thresholds = thresholds
+        self.Q = thresholds.Q
+        if not 1 <= self.Q <= _lib.TECM_EVENT_MAX_Q:
+            raise ValueError(f"between 1 and {_lib.TECM_EVENT_MAX_Q} thresholds, got {self.Q}")
+        if thresholds.num_nodes not in (None, self.I):
+            raise ValueError(f"the thresholds hold {thresholds.num_nodes} nodes, the forecast {self.I}")
+        self.scaler = _scaler_params(scaler)
+        self.thr = thresholds.tensor(device)
+        # [g][q][h][j][e][i]: node-contiguous, the layout the kernel's lanes read and write
+        self.hist = torch.zeros(self.G, self.Q, self.H, self.K + 1, 2, self.I, device=device, dtype=torch.int32)
+        self.grid, self.scales, self.sums = None, tuple(int(w) for w in scales), None
+        if grid is not None:
+            from tecmollm import ops
+            if self.K != 1:
+                raise ValueError("the FSS is taken of a deterministic forecast: grid needs members = 1")
+            self.grid = (int(grid[0]), int(grid[1]))
+            if self.grid[0] * self.grid[1] != self.I:
+                raise ValueError(f"grid {self.grid} does not hold {self.I} nodes")
+            if not 1 <= len(self.scales) <= _lib.TECM_EVENT_MAX_W or any(w < 1 or w > 127 or w % 2 == 0 for w in self.scales):
+                raise ValueError(f"scales must be 1 to {_lib.TECM_EVENT_MAX_W} odd widths in [1, 127], got {self.scales}")
+            if not ops.event_fss_ok(*self.grid):
+                raise TecmError(f"tecm_event_fss does not serve a {self.grid[0]} x {self.grid[1]} grid (its tables exceed 64 KiB of LDS)")
+            self.sums = torch.zeros(self.G, self.Q, self.H, len(self.scales), 3, device=device, dtype=torch.int64)
+
+    def reset(self) -> None:
+        self.hist.zero_()
+        if self.sums is not None:
+            self.sums.zero_()
+
+    def update(self, pred_or_members: torch.Tensor, y_true_scaled: torch.Tensor, groups: Optional[torch.Tensor] = None,
+               slots: Optional[torch.Tensor] = None) -> None:
+        """members = 1: the forecast (S, H, N) or (S, H, N, 1); members = K > 1: (K, S, H, N) or (K, S, H, N, 1); the truth
+        (S, H, N) or (S, H, N, 1); all in scaled units and read in place whatever their strides.  groups (S) int32 or None;
+        slots (S, H) int32, the time-of-day slot of every target step (`tecmollm.events.target_slots`), needed exactly when
+        the thresholds depend on the slot."""
+        from tecmollm import devcheck, ops
+        t, S, H, I, ts, th, ti = _as_shi(y_true_scaled, "y_true")
+        if self.K == 1:
+            p, S2, H2, I2, ps, ph, pi = _as_shi(pred_or_members, "y_pred")
+            m = p.as_strided((1, S2, H2, I2), (0, ps, ph, pi))
+        else:
+            m = pred_or_members
+            _lib.require_gpu_tensor(m, "members")
+            if m.dim() == 5 and m.shape[-1] == 1:
+                m = m.squeeze(-1)
+            if m.dim() != 4:
+                raise ValueError(f"members must be (K, S, H, N), got {tuple(pred_or_members.shape)}")
+        if tuple(m.shape) != (self.K, S, H, I) or H != self.H or I != self.I:
+            raise ValueError(f"shape mismatch: forecast {tuple(pred_or_members.shape)}, true {tuple(y_true_scaled.shape)}, "
+                             f"expected members {self.K}, horizons {self.H}, nodes {self.I}")
+        if groups is not None:
+            _lib.require_gpu_tensor(groups, "groups", torch.int32)
+            if groups.shape != (S,):
+                raise ValueError(f"groups must hold one id per sample: {tuple(groups.shape)} for {S} samples")
+            groups = groups.contiguous()
+        num_slots = self.thresholds.num_slots
+        if (slots is None) != (num_slots == 1):
+            raise ValueError("slots are needed exactly when the thresholds depend on the time-of-day slot")
+        if slots is not None:
+            _lib.require_gpu_tensor(slots, "slots", torch.int32)
+            if slots.shape != (S, H):
+                raise ValueError(f"slots must be (S, H) = {(S, H)}, got {tuple(slots.shape)}")
+            slots = slots.contiguous()
+        mean, scale = self.scaler if self.scaler is not None else (0.0, 1.0)
+        errs = devcheck.error_word(self.hist.device)
+        target = t.as_strided((S, H, I), (ts, th, ti))
+        common = dict(slots=slots, num_slots=num_slots, mean=mean, scale=scale,
+                      clip=(TEC_MIN, TEC_MAX) if self.scaler is not None else None, groups=groups, err_flag=errs.ptr())
+        ops.event_hist(m, target, self.hist, self.thr, self.thresholds.strides, self.thresholds.dirs, **common)
+        if self.sums is not None:
+            ops.event_fss(m[0], target, self.sums, self.thr, self.thresholds.strides, self.thresholds.dirs, self.scales,
+                          self.grid, **common)
+        if groups is not None or slots is not None:
+            errs.post()                        # only a group or slot id can set the word here
+
+    def merge_(self, group=None) -> "EventMetrics":
+        """Sum the counts (and the FSS sums) over the ranks of `group`, in place: all of them live in one int64 buffer for
+        the length of ONE all-reduce.  See `HorizonMetrics.merge_`."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            n = self.hist.numel()
+            parts = [self.hist.reshape(-1).to(torch.int64)] + ([self.sums.reshape(-1)] if self.sums is not None else [])
+            flat = torch.cat(parts)
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+            self.hist.copy_(flat[:n].view_as(self.hist).to(torch.int32))
+            if self.sums is not None:
+                self.sums.copy_(flat[n:].view_as(self.sums))
+        return self
+
+    def compute(self) -> Dict[str, object]:
+        """`derive_events` of the counts (and `derive_fss` of the sums, with the pooled base rate), plus "thresholds" (the
+        labels), "members" and, with a grid, "scales"."""
+        out: Dict[str, object] = dict(derive_events(self.hist.cpu().numpy().astype(np.int64)))
+        if self.sums is not None:
+            out.update(derive_fss(self.sums.cpu().numpy(), out["base_rate_pooled"]))
+            out["scales"] = list(self.scales)
+        out["thresholds"] = list(self.thresholds.labels)
+        out["members"] = self.K
         return out

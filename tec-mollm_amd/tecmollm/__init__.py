@@ -4,8 +4,8 @@ Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
   csrc/            hand-written HIP kernels + the C ABI (include/tecmollm.h at the repo root)
   tecmollm/        ctypes binding, autograd stage functions, graph preparation, training-step helpers, test-split evaluation,
                    input attribution, ensemble forecasts and their scores, spatial and temporal attention maps, conformal
-                   prediction intervals, significance of the comparison (block bootstrap, Diebold-Mariano), raw-data
-                   preprocessing
+                   prediction intervals, significance of the comparison (block bootstrap, Diebold-Mariano), event verification
+                   (contingency scores, Brier, ROC, FSS), raw-data preprocessing
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/features/    mirror of the reference's feature engineering (`from src.features.feature_engineering import ...`)
   src/data/        mirrors of the reference's dataset and data loader, and the series-backed SeriesWindowDataset
@@ -28,6 +28,8 @@ from .temporal_attention import (TemporalAttentionStats, evaluate_temporal_atten
 from . import significance  # noqa: F401
 from .significance import (WindowScores, block_bootstrap, bootstrap_intervals, diebold_mariano,  # noqa: F401
                            evaluate_significance, score_windows, write_significance)
+from . import events  # noqa: F401
+from .events import EventThresholds, evaluate_events, target_slots, write_events  # noqa: F401
 from . import preprocess  # noqa: F401
 from .preprocess import DeviceStandardScaler, preprocess_splits  # noqa: F401
 
@@ -39,4 +41,5 @@ __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradien
            "calibrate_conformal", "conformal_forecast", "evaluate_conformal", "write_conformal", "temporal_attention",
            "TemporalAttentionStats", "evaluate_temporal_attention", "write_temporal_attention", "preprocess", "DeviceStandardScaler",
            "preprocess_splits", "significance", "WindowScores", "score_windows", "block_bootstrap", "bootstrap_intervals",
-           "diebold_mariano", "evaluate_significance", "write_significance"]
+           "diebold_mariano", "evaluate_significance", "write_significance", "events", "EventThresholds", "target_slots",
+           "evaluate_events", "write_events"]

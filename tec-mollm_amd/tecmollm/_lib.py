@@ -217,6 +217,37 @@ class TecmBlockBootstrap(C.Structure):
     ]
 
 
+class TecmEventHist(C.Structure):
+    _fields_ = [
+        ("members", c_f32p), ("m_stride_k", C.c_int64), ("m_stride_s", C.c_int64), ("m_stride_h", C.c_int64),
+        ("m_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("G", C.c_int32), ("I", C.c_int64),
+        ("K", C.c_int32), ("Q", C.c_int32),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("num_slots", C.c_int32),
+        ("thr", c_f32p), ("th_stride_q", C.c_int64), ("th_stride_k", C.c_int64), ("th_stride_i", C.c_int64),
+        ("slot", C.c_void_p),
+        ("dir", C.c_int32 * 8),
+        ("hist", C.c_void_p), ("group", C.c_void_p), ("err_flag", C.c_void_p),
+    ]
+
+
+class TecmEventFss(C.Structure):
+    _fields_ = [
+        ("pred", c_f32p), ("p_stride_s", C.c_int64), ("p_stride_h", C.c_int64), ("p_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("G", C.c_int32), ("I", C.c_int64),
+        ("rows", C.c_int32), ("cols", C.c_int32), ("Q", C.c_int32), ("W", C.c_int32),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("num_slots", C.c_int32),
+        ("thr", c_f32p), ("th_stride_q", C.c_int64), ("th_stride_k", C.c_int64), ("th_stride_i", C.c_int64),
+        ("slot", C.c_void_p),
+        ("dir", C.c_int32 * 8), ("widths", C.c_int32 * 8),
+        ("sums", C.c_void_p), ("group", C.c_void_p), ("err_flag", C.c_void_p),
+    ]
+
+
 class TecmWindowBatch(C.Structure):
     _fields_ = [
         ("X", c_f32p), ("TF", c_f32p), ("Y", c_f32p), ("starts", C.c_void_p), ("starts_host_check", C.c_void_p),
@@ -355,6 +386,8 @@ TECM_CONF_ABS, TECM_CONF_SIGNED = 0, 1
 TECM_INTERVAL_STATS = 6
 TECM_SELECT_MAX_Q = 8
 TECM_BAD_ROW, TECM_BAD_START = 32, 64
+TECM_BAD_SLOT = 128
+TECM_EVENT_MAX_Q, TECM_EVENT_MAX_W, TECM_EVENT_LDS_WORDS = 8, 8, 256
 TECM_ATTN_SKIP_UNCONNECTED = 1
 TECM_TATT_COUNT = 8
 TECM_BASELINE_MEAN, TECM_BASELINE_LAST, TECM_BASELINE_PERIODIC = 0, 1, 2
@@ -463,6 +496,9 @@ EXPORTS = {
     "tecm_metrics_accumulate": (C.c_int, [C.POINTER(TecmMetrics), C.c_void_p]),
     "tecm_metrics_map": (C.c_int, [C.POINTER(TecmMetricsMap), C.c_void_p]),
     "tecm_ensemble_stats": (C.c_int, [C.POINTER(TecmEnsemble), C.c_void_p]),
+    "tecm_event_hist": (C.c_int, [C.POINTER(TecmEventHist), C.c_void_p]),
+    "tecm_event_fss": (C.c_int, [C.POINTER(TecmEventFss), C.c_void_p]),
+    "tecm_event_fss_supported": (C.c_int, [C.c_int32, C.c_int32]),
     "tecm_conformal_scores": (C.c_int, [C.POINTER(TecmConformalScores), C.c_void_p]),
     "tecm_column_select": (C.c_int, [C.POINTER(TecmColumnSelect), C.c_void_p]),
     "tecm_interval_stats": (C.c_int, [C.POINTER(TecmIntervalStats), C.c_void_p]),

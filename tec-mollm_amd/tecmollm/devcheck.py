@@ -15,7 +15,9 @@ synchronisation to the step:
 Bit 4 (TECM_BAD_GROUP) is set by the per-cell evaluation statistics (`MapMetrics.update`) when a sample's group id lies
 outside [0, num_groups): the sample is skipped, and `poll()` raises `TecmError`.  Bits 5 and 6 (TECM_BAD_ROW, TECM_BAD_START)
 are set by the significance kernels (`WindowScores.update`: a table row outside the table; `block_bootstrap`: a block start
-outside [0, S)) and raise `TecmError` too.  Bit 16 is used by the data-parallel
+outside [0, S)) and raise `TecmError` too.  Bit 7 (TECM_BAD_SLOT) is set by the event-verification kernels
+(`EventMetrics.update`) when a time-of-day slot id lies outside [0, num_slots): that (sample, horizon) is skipped, and
+`poll()` raises `TecmError`.  Bit 16 is used by the data-parallel
 rank-divergence check (tecmollm/train.py).
 """
 from __future__ import annotations
@@ -29,6 +31,7 @@ from ._lib import TecmError
 BAD_TOD, BAD_DOY, BAD_YEAR, BAD_SEASON = 1, 2, 4, 8
 BAD_GROUP = 16
 BAD_ROW, BAD_START = 32, 64
+BAD_SLOT = 128
 RANKS_DIVERGED = 1 << 16
 
 _NAMES = {BAD_TOD: "time-of-day index outside [0, 12)", BAD_DOY: "day-of-year index outside [0, 366)",
@@ -36,6 +39,7 @@ _NAMES = {BAD_TOD: "time-of-day index outside [0, 12)", BAD_DOY: "day-of-year in
           BAD_GROUP: "group id outside [0, num_groups) (the sample was skipped)",
           BAD_ROW: "table row outside [0, table_rows) (nothing was written)",
           BAD_START: "bootstrap block start outside [0, S) (the block was skipped)",
+          BAD_SLOT: "threshold slot id outside [0, num_slots) (the (sample, horizon) was skipped)",
           RANKS_DIVERGED: "data-parallel ranks no longer hold identical parameters"}
 
 
@@ -74,9 +78,9 @@ class DeviceErrorWord:
             self.event = None
             what = "; ".join(text for bit, text in _NAMES.items() if code & bit)
             if not (code & 15):
-                if code & (BAD_GROUP | BAD_ROW | BAD_START):
+                if code & (BAD_GROUP | BAD_ROW | BAD_START | BAD_SLOT):
                     flags = ", ".join(n for b, n in ((BAD_GROUP, "TECM_BAD_GROUP"), (BAD_ROW, "TECM_BAD_ROW"),
-                                                     (BAD_START, "TECM_BAD_START")) if code & b)
+                                                     (BAD_START, "TECM_BAD_START"), (BAD_SLOT, "TECM_BAD_SLOT")) if code & b)
                     raise TecmError(f"device error word = {code:#x} ({flags}): {what}")
                 raise RuntimeError(f"device error word = {code:#x}: {what}")
             raise IndexError(f"index out of range in self (device error word = {code:#x}): {what} -- the reference's "

@@ -853,6 +853,78 @@ def ensemble_stats(members: torch.Tensor, target: torch.Tensor, stats: torch.Ten
     check(lib().tecm_ensemble_stats(C.byref(e), stream_ptr()), "tecm_ensemble_stats")
 
 
+def _event_common(thr: torch.Tensor, thr_strides, dirs, slots, num_slots: int, S: int, H: int):
+    _lib.require_gpu_tensor(thr, "thresholds", torch.float32)
+    Q = len(dirs)
+    if len(thr_strides) != 3 or min(int(v) for v in thr_strides) < 0:
+        raise ValueError(f"thr_strides must be three non-negative element strides (q, slot, node), got {thr_strides}")
+    if slots is not None:
+        _lib.require_gpu_tensor(slots, "slots", torch.int32)
+        if slots.shape != (S, H) or not slots.is_contiguous():
+            raise ValueError(f"slots must be a contiguous int32 ({S}, {H}) tensor, got {tuple(slots.shape)}")
+    elif int(num_slots) != 1:
+        raise ValueError("num_slots must be 1 without a slot tensor")
+    d = (C.c_int32 * 8)(*[int(v) for v in list(dirs)[:8]])
+    return Q, d
+
+
+def event_hist(members: torch.Tensor, target: torch.Tensor, hist: torch.Tensor, thr: torch.Tensor, thr_strides, dirs, *,
+               slots: Optional[torch.Tensor] = None, num_slots: int = 1, mean: float = 0.0, scale: float = 1.0,
+               clip: Optional[Tuple[float, float]] = None, groups: Optional[torch.Tensor] = None, err_flag: int = 0) -> None:
+    """tecm_event_hist (include/tecmollm.h (3j a)): one update of `hist` (G, Q, H, K+1, 2, I) int32 (read as unsigned counts)
+    from `members` (K, S, H, I) and `target` (S, H, I), float32 views of any strides, read in place.  `thr` is a float32
+    device tensor addressed with the element strides `thr_strides` = (q, slot, node), any of which may be 0; `dirs` holds
+    one non-zero int per threshold (> 0: above, < 0: below); `slots` (S, H) int32 or None."""
+    K, S, H, I = members.shape
+    if target.shape != (S, H, I):
+        raise ValueError(f"target must be (S, H, I) = {(S, H, I)}, got {tuple(target.shape)}")
+    Q, d = _event_common(thr, thr_strides, dirs, slots, num_slots, S, H)
+    G = hist.shape[0]
+    if hist.shape != (G, Q, H, K + 1, 2, I) or hist.dtype != torch.int32 or not hist.is_contiguous():
+        raise ValueError(f"hist must be a contiguous int32 (G, {Q}, {H}, {K + 1}, 2, {I}) tensor")
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    e = _lib.TecmEventHist(members=members.data_ptr(), m_stride_k=members.stride(0), m_stride_s=members.stride(1),
+                           m_stride_h=members.stride(2), m_stride_i=members.stride(3),
+                           target=target.data_ptr(), t_stride_s=target.stride(0), t_stride_h=target.stride(1),
+                           t_stride_i=target.stride(2), S=S, H=H, G=G, I=I, K=K, Q=Q, mean=float(mean), scale=float(scale),
+                           clip_lo=lo, clip_hi=hi, clip=1 if clip is not None else 0, num_slots=int(num_slots),
+                           thr=thr.data_ptr(), th_stride_q=int(thr_strides[0]), th_stride_k=int(thr_strides[1]),
+                           th_stride_i=int(thr_strides[2]), slot=ptr(slots), dir=d, hist=hist.data_ptr(),
+                           group=ptr(groups), err_flag=err_flag or None)
+    check(lib().tecm_event_hist(C.byref(e), stream_ptr()), "tecm_event_hist")
+
+
+def event_fss_ok(rows: int, cols: int) -> bool:
+    """Whether tecm_event_fss serves a rows x cols grid (tecm_event_fss_supported: its LDS map in 64 KiB)."""
+    return lib().tecm_event_fss_supported(int(rows), int(cols)) == 1
+
+
+def event_fss(pred: torch.Tensor, target: torch.Tensor, sums: torch.Tensor, thr: torch.Tensor, thr_strides, dirs, widths,
+              grid, *, slots: Optional[torch.Tensor] = None, num_slots: int = 1, mean: float = 0.0, scale: float = 1.0,
+              clip: Optional[Tuple[float, float]] = None, groups: Optional[torch.Tensor] = None, err_flag: int = 0) -> None:
+    """tecm_event_fss (include/tecmollm.h (3j b)): one update of `sums` (G, Q, H, W, 3) int64 (read as unsigned sums) from a
+    deterministic forecast `pred` and `target`, (S, H, I) float32 views read in place, on the (rows, cols) `grid` with
+    I == rows * cols, for the odd window `widths`.  Thresholds, directions and slots as in `event_hist`."""
+    S, H, I = pred.shape
+    if target.shape != (S, H, I):
+        raise ValueError(f"target must be (S, H, I) = {(S, H, I)}, got {tuple(target.shape)}")
+    Q, d = _event_common(thr, thr_strides, dirs, slots, num_slots, S, H)
+    W, G = len(widths), sums.shape[0]
+    if sums.shape != (G, Q, H, W, 3) or sums.dtype != torch.int64 or not sums.is_contiguous():
+        raise ValueError(f"sums must be a contiguous int64 (G, {Q}, {H}, {W}, 3) tensor")
+    wd = (C.c_int32 * 8)(*[int(v) for v in list(widths)[:8]])
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    e = _lib.TecmEventFss(pred=pred.data_ptr(), p_stride_s=pred.stride(0), p_stride_h=pred.stride(1),
+                          p_stride_i=pred.stride(2), target=target.data_ptr(), t_stride_s=target.stride(0),
+                          t_stride_h=target.stride(1), t_stride_i=target.stride(2), S=S, H=H, G=G, I=I, rows=int(grid[0]),
+                          cols=int(grid[1]), Q=Q, W=W, mean=float(mean), scale=float(scale), clip_lo=lo, clip_hi=hi,
+                          clip=1 if clip is not None else 0, num_slots=int(num_slots), thr=thr.data_ptr(),
+                          th_stride_q=int(thr_strides[0]), th_stride_k=int(thr_strides[1]), th_stride_i=int(thr_strides[2]),
+                          slot=ptr(slots), dir=d, widths=wd, sums=sums.data_ptr(), group=ptr(groups),
+                          err_flag=err_flag or None)
+    check(lib().tecm_event_fss(C.byref(e), stream_ptr()), "tecm_event_fss")
+
+
 CONFORMAL_MODES = {"absolute": _lib.TECM_CONF_ABS, "signed": _lib.TECM_CONF_SIGNED}
 INTERVAL_OUTPUTS = ("lo", "hi", "mid")
 

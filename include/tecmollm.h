@@ -1295,6 +1295,106 @@ typedef struct {
 } TecmLinForecast;
 int tecm_lin_forecast(const TecmLinForecast* f, void* stream);
 
+/* (3k) quantile forecasts: the pinball loss a quantile model is trained with (a), the scores a Q-level forecast is judged
+ * by per cell (g, h, i) (b), and the nonconformity score of conformalized quantile regression (c).
+ *
+ * LAYOUT CONVENTION (the one place it is stated): levels taus = (tau_1 < ... < tau_Q), 1 <= Q <= TECM_QUANT_MAX_Q, every
+ * tau in (0, 1).  A quantile model is TEC_MoLLM built with prediction_horizon = Q * L_out; output channel j = q*L_out + h
+ * holds level q (0-based) of horizon h, so out.view(B, Q, L_out, N) -- strided, no copy -- is the quantile tensor and level q
+ * alone a (B, L_out, N, 1) view.
+ *
+ * (a) tecm_pinball_fwd_bwd_strided: the mean pinball loss of pred (B, Q, H, N) against target (B, H, N), fused with its
+ *     gradient.  pred is addressed as pred[b*p_stride_b + q*p_stride_q + h*p_stride_h + n*p_stride_n], target as
+ *     target[b*t_stride_b + h*t_stride_h + n*t_stride_n] (element strides, 64-bit, read in place).  With M = B*H*N and
+ *       u   = y - p                                   (float32)
+ *       rho = (double)u * ((double)tau_q - [u < 0])   (float64)
+ *     the outputs are
+ *       loss_levels[q] = (float)((sum of rho over level q) / M)                  (optional, Q floats)
+ *       loss_out[0]    = (float)((sum of the Q level sums, q ascending) / (Q*M))
+ *       dpred          = g * ([u < 0] - tau_q),  g = grad_scale / (float)(Q*M)   (optional; float32: one division, one
+ *                        subtraction and one product), written at pred's offsets: dpred has pred's layout.
+ *     At u == 0 the gradient is the -tau branch ([u < 0] = 0): d rho / d p = -tau there, as for every u > 0.
+ *     Order of the sums (float64, fixed, no atomics): block (x, q) of nbx = min(ceil(M / 256), TECM_PINBALL_BLOCK_CAP) x Q
+ *     blocks of 256 threads walks the elements e = x*256 + t, + nbx*256, ... of level q's (b, h, n) space in ascending
+ *     order per thread; the 64 partials of a wave are halved six times (v += v[l ^ o], o = 32 .. 1), the four waves added as
+ *     (w0 + w1) + (w2 + w3) into workspace[q*nbx + x]; a second one-block stage adds every level's nbx partials the same
+ *     way (thread t: x = t, t + 256, ...).  Element e decodes with h fastest when p_stride_n != 1 (the head's (B, N, Q*H)
+ *     storage: p_stride_h == 1) and with n fastest when p_stride_n == 1, so lanes run along whichever is contiguous.
+ *     workspace: Q * nbx doubles.  Limits: Q*M < 2^53; no value is filtered: a NaN operand gives a NaN loss. */
+#define TECM_QUANT_MAX_Q 16
+#define TECM_PINBALL_BLOCK_CAP 1024
+typedef struct {
+  const float* pred; int64_t p_stride_b, p_stride_q, p_stride_h, p_stride_n;
+  const float* target; int64_t t_stride_b, t_stride_h, t_stride_n;
+  int32_t B, Q, H, N;
+  float taus[TECM_QUANT_MAX_Q];
+  float grad_scale; int32_t _pad;
+  float* dpred;                  /* NULL: loss only */
+  float* loss_out;
+  float* loss_levels;            /* NULL: not wanted */
+  double* workspace;
+} TecmPinball;
+int tecm_pinball_fwd_bwd_strided(const TecmPinball* p, void* stream);
+
+/* (b) tecm_quantile_stats: the Q levels, addressed as levels[q*l_stride_q + s*l_stride_s + h*l_stride_h + i*l_stride_i], and
+ *     the target (as in (3b)) go through the value pipeline of (3) / (3b) (non-finite scaled value -> 0, inverse transform
+ *     with two f32 roundings, nan_to_num, optional clip of the levels only), which leaves float32 x_1..x_Q and y.  Per
+ *     (sample, horizon, node), with P = Q / 2 (integer division):
+ *       crossing c = [there is a q with x_q > x_{q+1}]
+ *       z        = x sorted ascending (the rearrangement), then z_q = z_q + adjust[((ga*H + h)*Q + q)*I + i] in float32 when
+ *                  adjust (Ga, H, Q, I) is given; ga = g when Ga == G and 0 when Ga == 1
+ *       rho_q    = ((double)y - (double)z_q) * ((double)tau_q - [y < z_q])
+ *       hit b_q  = [y <= z_q]
+ *       pair r = 1..P:  lo = z_r, hi = z_{Q+1-r};  width = (double)hi - (double)lo (negative where adjust makes it so: not
+ *                  clamped),  covered = [lo <= y <= hi]
+ *     (one device function, quantile_sorted in csrc/quantile.hip, gives (c) the same z and y).  ACCUMULATED across samples and
+ *     calls into two node-contiguous arrays, index ((g*H + h)*(1 + Q + P) + n)*I + i:
+ *       stats   doubles: [count, sum rho_1..rho_Q, sum width_1..width_P]
+ *       counts  uint32:  [crossings, hits_1..hits_Q, covered_1..covered_P]
+ *     with the ownership and order of (3c): one wave per (tile of 64 nodes, horizon, group), lanes along the nodes, one
+ *     owning thread per cell adds its samples in ascending s in registers and adds to the arrays once: no atomics, the same
+ *     calls give the same bits; cells of a group that does not occur are neither read nor written; an id outside [0, G)
+ *     skips the sample everywhere and sets TECM_BAD_GROUP in *err_flag.  Q is served by the compile-time bucket 1, 2, 4, 8
+ *     or 16 (padding +inf sorts behind the finite levels).  Optional per-sample output: out_z[q*o_stride_q + s*o_stride_s +
+ *     h*o_stride_h + i*o_stride_i] = z_q, the (adjusted) sorted levels in physical units.  With target == NULL only out_z is
+ *     written (stats and counts may be NULL): the forecast path.
+ *     Limits: 1 <= Q <= TECM_QUANT_MAX_Q, G and H <= 65535, scale != 0. */
+typedef struct {
+  const float* levels; int64_t l_stride_q, l_stride_s, l_stride_h, l_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  int64_t S; int32_t H; int32_t G; int64_t I;          /* samples, horizons, groups, nodes */
+  int32_t Q; int32_t Ga;                               /* levels; groups of adjust (1 or G) */
+  float taus[TECM_QUANT_MAX_Q];
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  int32_t _pad2;
+  const float* adjust;           /* NULL: none */
+  double* stats;
+  uint32_t* counts;
+  const int32_t* group;
+  int32_t* err_flag;
+  float* out_z; int64_t o_stride_q, o_stride_s, o_stride_h, o_stride_i;
+} TecmQuantileStats;
+int tecm_quantile_stats(const TecmQuantileStats* c, void* stream);
+
+/* (c) tecm_quantile_scores: the CQR score (Romano, Patterson and Candes 2019) of the pair (lo_idx, hi_idx), 0-based indices
+ *     into the SORTED levels z of (b) (no adjust), in float32:
+ *       E = max(z_lo - y, y - z_hi),   scores[(row0 + s)*ld + h*I + i] = E
+ *     -- the addressing of tecm_conformal_scores (3g)(a), so tecm_column_select selects from the store unchanged.  The
+ *     interval [z_lo - Qhat, z_hi + Qhat] covers y exactly when E <= Qhat.
+ *     Limits: 0 <= lo_idx <= hi_idx < Q, ld >= H*I, row0 >= 0, ceil(H / 4) <= 65535, scale != 0. */
+typedef struct {
+  const float* levels; int64_t l_stride_q, l_stride_s, l_stride_h, l_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  int64_t S; int32_t H; int32_t Q; int64_t I;
+  int32_t lo_idx, hi_idx;
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  int32_t _pad2;
+  float* scores; int64_t ld; int64_t row0;
+} TecmQuantileScores;
+int tecm_quantile_scores(const TecmQuantileScores* c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

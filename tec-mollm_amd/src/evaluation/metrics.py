@@ -504,6 +504,165 @@ class IntervalMetrics:
         return out
 
 
+# ------------------------------------------------------------------------------------ quantile forecasts
+QUANTILE_LEVEL_KEYS = ("pinball", "reliability")                              # (..., Q)
+QUANTILE_PAIR_KEYS = ("interval_width", "coverage", "interval_score")         # (..., P), P = Q // 2
+QUANTILE_KEYS = ("count", "crossing_rate", "quantile_crps") + QUANTILE_LEVEL_KEYS + QUANTILE_PAIR_KEYS
+
+
+def quantile_pairs(taus) -> Tuple[Tuple[float, float, float], ...]:
+    """The P = Q // 2 central intervals of the levels: pair r = (tau_r, tau_{Q+1-r}, alpha_r) with the nominal miscoverage
+    alpha_r = tau_r + 1 - tau_{Q+1-r}."""
+    ts = [float(t) for t in taus]
+    return tuple((ts[r], ts[len(ts) - 1 - r], ts[r] + 1.0 - ts[len(ts) - 1 - r]) for r in range(len(ts) // 2))
+
+
+def crps_weights(taus) -> np.ndarray:
+    """Trapezoid weights of the levels in tau: w_q = (tau_{q+1} - tau_{q-1}) / 2 inside, half the neighbouring gap at either
+    end; one level alone has the weight 1."""
+    ts = np.asarray([float(t) for t in taus], dtype=np.float64)
+    if ts.size == 1:
+        return np.ones(1)
+    w = np.empty_like(ts)
+    w[1:-1] = (ts[2:] - ts[:-2]) / 2
+    w[0], w[-1] = (ts[1] - ts[0]) / 2, (ts[-1] - ts[-2]) / 2
+    return w
+
+
+def derive_quantiles(stats: np.ndarray, counts: np.ndarray, taus) -> Dict[str, np.ndarray]:
+    """(..., 1 + Q + P) float64 sums [count, sum rho_1..Q, sum width_1..P] and integer counts [crossings, hits_1..Q,
+    covered_1..P] -> the QUANTILE_KEYS, arrays over the leading axes (a trailing axis of Q or P where named), NaN where a cell
+    saw no sample:
+      pinball_q = sum rho_q / n, reliability_q = hits_q / n (to be read against tau_q), crossing_rate = crossings / n,
+      interval_width_r = sum width_r / n, coverage_r = covered_r / n, and, derived from the pinball means,
+      interval_score_r = (2 / alpha_r) (pinball_r + pinball_{Q+1-r})    with alpha_r = tau_r + 1 - tau_{Q+1-r}: the Winkler
+                         score of the pair -- for a symmetric pair (tau, 1 - tau) exactly width + (2/alpha) (lo - y)_+ +
+                         (2/alpha) (y - hi)_+ averaged over the samples,
+      quantile_crps    = 2 sum_q w_q pinball_q    with the trapezoid weights `crps_weights(taus)`: the CRPS integral
+                         2 * int_0^1 rho_tau d tau on the levels at hand."""
+    ts = [float(t) for t in taus]
+    Q, P = len(ts), len(ts) // 2
+    st = np.asarray(stats, dtype=np.float64)
+    ct = np.asarray(counts).astype(np.float64)
+    if st.shape[-1] != 1 + Q + P or ct.shape != st.shape:
+        raise ValueError(f"stats and counts must be (..., {1 + Q + P}), got {st.shape} and {ct.shape}")
+    n = st[..., 0]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        nn = n[..., None]
+        pin = st[..., 1:1 + Q] / nn
+        out = {"count": n.copy(), "crossing_rate": ct[..., 0] / n, "pinball": pin, "reliability": ct[..., 1:1 + Q] / nn,
+               "interval_width": st[..., 1 + Q:] / nn, "coverage": ct[..., 1 + Q:] / nn}
+        pairs = quantile_pairs(ts)
+        out["interval_score"] = np.stack([(2.0 / a) * (pin[..., r] + pin[..., Q - 1 - r]) for r, (_, _, a) in enumerate(pairs)],
+                                         axis=-1) if P else np.empty(n.shape + (0,))
+        w = crps_weights(ts)
+        acc = np.zeros_like(n)
+        for q in range(Q):
+            acc = acc + w[q] * pin[..., q]
+        out["quantile_crps"] = 2.0 * acc
+    empty = n == 0
+    for k in QUANTILE_KEYS[1:]:
+        out[k] = np.where(empty if out[k].ndim == n.ndim else empty[..., None], np.nan, out[k])
+    return out
+
+
+def _pooled_quantiles(per: Dict[str, np.ndarray]) -> Dict[str, object]:
+    """`derive_quantiles` of (H, ...) rows -> per key its list by horizon and the average over the horizons."""
+    out: Dict[str, object] = {"count_by_horizon": per["count"].tolist()}
+    for k in QUANTILE_KEYS[1:]:
+        out[f"{k}_by_horizon"] = per[k].tolist()
+        out[f"{k}_avg"] = np.mean(per[k], axis=0).tolist() if per[k].ndim > 1 else float(np.mean(per[k]))
+    return out
+
+
+class QuantileMetrics:
+    """The scores of a Q-level quantile forecast per cell (group of the sample, horizon, node): per-level pinball loss and
+    reliability, the crossing rate, width, coverage and Winkler score of the Q // 2 central intervals, and the quantile CRPS.
+    update(levels, true, groups) per batch on the device (one kernel, `tecm_quantile_stats`, no atomics: the same batches
+    give the same bits), compute() at the end.  It mirrors `EnsembleMetrics`; the layout convention of the levels is stated
+    in include/tecmollm.h (3k)."""
+
+    def __init__(self, num_horizons: int, num_nodes: int, taus, num_groups: int = 1, scaler=None,
+                 device: Union[str, torch.device] = "cuda"):
+        from tecmollm.functions import quantile_levels
+        self.H, self.I, self.G = int(num_horizons), int(num_nodes), int(num_groups)
+        if min(self.H, self.I, self.G) < 1:
+            raise ValueError("QuantileMetrics needs at least one horizon, one node and one group")
+        self.taus = quantile_levels(taus)
+        self.Q, self.P = len(self.taus), len(self.taus) // 2
+        self.scaler = _scaler_params(scaler)
+        rows = 1 + self.Q + self.P
+        # [g][h][k][i]: node-contiguous, the layout the kernel's lanes read and write
+        self.stats = torch.zeros(self.G, self.H, rows, self.I, device=device, dtype=torch.float64)
+        self.counts = torch.zeros(self.G, self.H, rows, self.I, device=device, dtype=torch.int32)
+
+    def reset(self) -> None:
+        self.stats.zero_()
+        self.counts.zero_()
+
+    def update(self, levels_scaled: torch.Tensor, y_true_scaled: Optional[torch.Tensor], groups: Optional[torch.Tensor] = None,
+               adjust: Optional[torch.Tensor] = None, want_sorted: bool = False) -> Optional[torch.Tensor]:
+        """levels (S, Q, H, N) in scaled units -- `QuantileModel.quantiles`, read in place whatever its strides --, truth
+        (S, H, N) or (S, H, N, 1) or None (nothing is accumulated, only the sorted levels are made); groups (S) int32 or
+        None; adjust a contiguous float32 (1 or G, H, Q, N) device tensor added to the sorted levels (`CQRIntervals.on`).
+        With `want_sorted` returns the (adjusted) sorted levels in physical units, (S, Q, H, N) float32."""
+        from tecmollm import devcheck, ops
+        _lib.require_gpu_tensor(levels_scaled, "levels")
+        if levels_scaled.dim() != 4 or tuple(levels_scaled.shape[1:]) != (self.Q, self.H, self.I):
+            raise ValueError(f"levels must be (S, {self.Q}, {self.H}, {self.I}), got {tuple(levels_scaled.shape)}")
+        S = levels_scaled.shape[0]
+        truth = None
+        if y_true_scaled is not None:
+            t, S2, H2, I2, ts, th, ti = _as_shi(y_true_scaled, "y_true")
+            if (S2, H2, I2) != (S, self.H, self.I):
+                raise ValueError(f"shape mismatch: levels {tuple(levels_scaled.shape)}, y_true {tuple(y_true_scaled.shape)}")
+            truth = t.as_strided((S, self.H, self.I), (ts, th, ti))
+        if groups is not None:
+            _lib.require_gpu_tensor(groups, "groups", torch.int32)
+            if groups.shape != (S,):
+                raise ValueError(f"groups must hold one id per sample: {tuple(groups.shape)} for {S} samples")
+            groups = groups.contiguous()
+        mean, scale = self.scaler if self.scaler is not None else (0.0, 1.0)
+        errs = devcheck.error_word(self.stats.device)
+        out = None
+        if want_sorted or truth is None:
+            out = torch.empty(S, self.Q, self.H, self.I, device=levels_scaled.device, dtype=torch.float32)
+        ops.quantile_stats(levels_scaled.permute(1, 0, 2, 3), truth, self.taus, self.stats, self.counts, adjust=adjust,
+                           mean=mean, scale=scale, clip=(TEC_MIN, TEC_MAX) if self.scaler is not None else None,
+                           groups=groups, num_groups=self.G, err_flag=errs.ptr(),
+                           out_z=out.permute(1, 0, 2, 3) if out is not None else None)
+        if groups is not None:
+            errs.post()                        # only a group id can set the word here
+        return out
+
+    def merge_(self, group=None) -> "QuantileMetrics":
+        """Sum the statistics over the ranks of `group` with ONE all-reduce, in place (see `HorizonMetrics.merge_`): the
+        counts ride behind the sums as float64 (integers below 2^53: exact)."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            both = torch.stack([self.stats, (self.counts.to(torch.int64) & 0xFFFFFFFF).to(torch.float64)])   # unsigned counts
+            dist.all_reduce(both, op=dist.ReduceOp.SUM, group=group)
+            self.stats.copy_(both[0])
+            self.counts.copy_(both[1].to(torch.int64))
+        return self
+
+    def compute(self) -> Dict[str, object]:
+        """The QUANTILE_KEYS as numpy arrays (G, H, N), with a trailing axis of Q for `pinball` and `reliability` and of
+        P = Q // 2 for `interval_width`, `coverage` and `interval_score` (`derive_quantiles` states the formulas), NaN where a
+        cell saw no sample; "taus"; "pairs": per central interval (tau_lo, tau_hi, alpha); "by_group": per group the scores
+        of its statistics pooled over the nodes, by horizon and averaged over the horizons."""
+        st = self.stats.permute(0, 1, 3, 2).cpu().numpy()                   # (G, H, I, 1 + Q + P)
+        ct = self.counts.permute(0, 1, 3, 2).cpu().numpy().astype(np.int64)
+        if self.counts.dtype == torch.int32:
+            ct &= 0xFFFFFFFF                                                # the kernel counts unsigned
+        out: Dict[str, object] = dict(derive_quantiles(st, ct, self.taus))
+        out["taus"] = list(self.taus)
+        out["pairs"] = [list(p) for p in quantile_pairs(self.taus)]
+        out["by_group"] = [_pooled_quantiles(derive_quantiles(st[g].sum(axis=1), ct[g].sum(axis=1), self.taus))
+                           for g in range(self.G)]
+        return out
+
+
 # ------------------------------------------------------------------------------------ event verification
 EVENT_CATEGORICAL_KEYS = ("base_rate", "pod", "far", "pofd", "csi", "ets", "hss", "frequency_bias")
 EVENT_PROBABILISTIC_KEYS = ("brier", "brier_reliability", "brier_resolution", "brier_uncertainty", "brier_skill", "roc_area")

@@ -5,7 +5,8 @@ Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
   tecmollm/        ctypes binding, autograd stage functions, graph preparation, training-step helpers, test-split evaluation,
                    input attribution, ensemble forecasts and their scores, spatial and temporal attention maps, conformal
                    prediction intervals, significance of the comparison (block bootstrap, Diebold-Mariano), event verification
-                   (contingency scores, Brier, ROC, FSS), raw-data preprocessing
+                   (contingency scores, Brier, ROC, FSS), quantile forecasts (pinball-loss training, quantile scores,
+                   conformalized quantile regression), raw-data preprocessing
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/features/    mirror of the reference's feature engineering (`from src.features.feature_engineering import ...`)
   src/data/        mirrors of the reference's dataset and data loader, and the series-backed SeriesWindowDataset
@@ -14,7 +15,7 @@ Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
 from ._lib import LIB_PATH, TecmError, lib  # noqa: F401
 from .devcheck import check_device_errors  # noqa: F401
 from .attribute import attribution_maps, input_gradient, integrated_gradients, write_attributions  # noqa: F401
-from .functions import dropout_seed  # noqa: F401
+from .functions import PinballFn, PinballLoss, dropout_seed  # noqa: F401
 from . import ensemble  # noqa: F401
 from .ensemble import (ensemble_forecast, ensemble_members, evaluate_ensemble, member_seed,  # noqa: F401
                        write_ensemble)
@@ -30,6 +31,9 @@ from .significance import (WindowScores, block_bootstrap, bootstrap_intervals, d
                            evaluate_significance, score_windows, write_significance)
 from . import events  # noqa: F401
 from .events import EventThresholds, evaluate_events, target_slots, write_events  # noqa: F401
+from . import quantile  # noqa: F401
+from .quantile import (CQRIntervals, QuantileModel, calibrate_cqr, evaluate_quantiles, quantile_config,  # noqa: F401
+                       quantile_forecast, write_quantiles)
 from . import preprocess  # noqa: F401
 from .preprocess import DeviceStandardScaler, preprocess_splits  # noqa: F401
 
@@ -42,4 +46,5 @@ __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradien
            "TemporalAttentionStats", "evaluate_temporal_attention", "write_temporal_attention", "preprocess", "DeviceStandardScaler",
            "preprocess_splits", "significance", "WindowScores", "score_windows", "block_bootstrap", "bootstrap_intervals",
            "diebold_mariano", "evaluate_significance", "write_significance", "events", "EventThresholds", "target_slots",
-           "evaluate_events", "write_events"]
+           "evaluate_events", "write_events", "quantile", "PinballFn", "PinballLoss", "QuantileModel", "CQRIntervals",
+           "quantile_config", "quantile_forecast", "evaluate_quantiles", "calibrate_cqr", "write_quantiles"]

@@ -195,6 +195,51 @@ class TecmIntervalStats(C.Structure):
     ]
 
 
+TECM_QUANT_MAX_Q = 16
+TECM_PINBALL_BLOCK_CAP = 1024
+
+
+class TecmPinball(C.Structure):
+    _fields_ = [
+        ("pred", c_f32p), ("p_stride_b", C.c_int64), ("p_stride_q", C.c_int64), ("p_stride_h", C.c_int64),
+        ("p_stride_n", C.c_int64),
+        ("target", c_f32p), ("t_stride_b", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_n", C.c_int64),
+        ("B", C.c_int32), ("Q", C.c_int32), ("H", C.c_int32), ("N", C.c_int32),
+        ("taus", C.c_float * TECM_QUANT_MAX_Q),
+        ("grad_scale", C.c_float), ("_pad", C.c_int32),
+        ("dpred", c_f32p), ("loss_out", c_f32p), ("loss_levels", c_f32p), ("workspace", C.c_void_p),
+    ]
+
+
+class TecmQuantileStats(C.Structure):
+    _fields_ = [
+        ("levels", c_f32p), ("l_stride_q", C.c_int64), ("l_stride_s", C.c_int64), ("l_stride_h", C.c_int64),
+        ("l_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("G", C.c_int32), ("I", C.c_int64),
+        ("Q", C.c_int32), ("Ga", C.c_int32),
+        ("taus", C.c_float * TECM_QUANT_MAX_Q),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("_pad2", C.c_int32),
+        ("adjust", c_f32p), ("stats", C.c_void_p), ("counts", C.c_void_p), ("group", C.c_void_p), ("err_flag", C.c_void_p),
+        ("out_z", c_f32p), ("o_stride_q", C.c_int64), ("o_stride_s", C.c_int64), ("o_stride_h", C.c_int64),
+        ("o_stride_i", C.c_int64),
+    ]
+
+
+class TecmQuantileScores(C.Structure):
+    _fields_ = [
+        ("levels", c_f32p), ("l_stride_q", C.c_int64), ("l_stride_s", C.c_int64), ("l_stride_h", C.c_int64),
+        ("l_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("Q", C.c_int32), ("I", C.c_int64),
+        ("lo_idx", C.c_int32), ("hi_idx", C.c_int32),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("_pad2", C.c_int32),
+        ("scores", c_f32p), ("ld", C.c_int64), ("row0", C.c_int64),
+    ]
+
+
 class TecmMetricsWindow(C.Structure):
     _fields_ = [
         ("pred", c_f32p), ("p_stride_s", C.c_int64), ("p_stride_h", C.c_int64), ("p_stride_i", C.c_int64),
@@ -502,6 +547,9 @@ EXPORTS = {
     "tecm_conformal_scores": (C.c_int, [C.POINTER(TecmConformalScores), C.c_void_p]),
     "tecm_column_select": (C.c_int, [C.POINTER(TecmColumnSelect), C.c_void_p]),
     "tecm_interval_stats": (C.c_int, [C.POINTER(TecmIntervalStats), C.c_void_p]),
+    "tecm_pinball_fwd_bwd_strided": (C.c_int, [C.POINTER(TecmPinball), C.c_void_p]),
+    "tecm_quantile_stats": (C.c_int, [C.POINTER(TecmQuantileStats), C.c_void_p]),
+    "tecm_quantile_scores": (C.c_int, [C.POINTER(TecmQuantileScores), C.c_void_p]),
     "tecm_metrics_window": (C.c_int, [C.POINTER(TecmMetricsWindow), C.c_void_p]),
     "tecm_block_bootstrap": (C.c_int, [C.POINTER(TecmBlockBootstrap), C.c_void_p]),
     "tecm_window_batch": (C.c_int, [C.POINTER(TecmWindowBatch), C.c_void_p]),

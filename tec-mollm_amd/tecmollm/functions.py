@@ -13,11 +13,11 @@ import contextlib
 import os
 from dataclasses import dataclass
 import weakref
-from typing import Callable, List, Optional
+from typing import Callable, List, Optional, Tuple
 
 import torch
 
-from . import devcheck, ops
+from . import _lib, devcheck, ops
 from ._lib import TecmSpatial, TecmSpatialDx, TecmSpatialGrads, check, lib, stream_ptr
 from .graph import GraphMeta
 from .ops import (A_KM, A_MK, ACT_GELU_ERF, ACT_GELU_TANH, B_KN, B_NK, colsum, drop, gemm, pick_split_k, win)
@@ -1249,3 +1249,59 @@ class HuberFn(torch.autograd.Function):
     def backward(ctx, gloss):
         (dpred,) = ctx.saved_tensors
         return dpred * gloss, None, None
+
+
+def quantile_levels(taus) -> Tuple[float, ...]:
+    """The levels of a quantile forecast as a tuple of floats: between 1 and 16 of them (TECM_QUANT_MAX_Q), strictly
+    increasing, every one inside (0, 1).  Raises ValueError otherwise."""
+    ts = tuple(float(t) for t in taus)
+    if not 1 <= len(ts) <= _lib.TECM_QUANT_MAX_Q:
+        raise ValueError(f"between 1 and {_lib.TECM_QUANT_MAX_Q} quantile levels, got {len(ts)}")
+    if any(not 0.0 < t < 1.0 for t in ts):
+        raise ValueError(f"quantile levels must lie inside (0, 1), got {ts}")
+    if any(a >= b for a, b in zip(ts, ts[1:])):
+        raise ValueError(f"quantile levels must increase strictly (sorted, none repeated), got {ts}")
+    return ts
+
+
+def quantile_view(out: torch.Tensor, Q: int) -> torch.Tensor:
+    """The (B, Q, L_out, N) view of a model output (B, Q * L_out, N, 1) under the layout convention of include/tecmollm.h
+    (3k): channel j = q * L_out + h is level q of horizon h.  A view of any strides, never a copy."""
+    if out.dim() != 4 or out.shape[3] != 1 or out.shape[1] % Q:
+        raise ValueError(f"a quantile output is (B, Q * L_out, N, 1) with Q = {Q}, got {tuple(out.shape)}")
+    B, QL, N, _ = out.shape
+    sb, sj, sn, _ = out.stride()
+    L = QL // Q
+    return out.as_strided((B, Q, L, N), (sb, L * sj, sj, sn), out.storage_offset())
+
+
+class PinballFn(torch.autograd.Function):
+    """Mean pinball (quantile) loss of the (B, Q * L_out, N, 1) output against y (B, L_out, N, 1) at the levels `taus`, loss
+    and gradient in one kernel pair (tecm_pinball_fwd_bwd_strided); at y == prediction the gradient is the -tau branch."""
+
+    @staticmethod
+    def forward(ctx, pred, target, taus):
+        loss, dpred, _ = ops.pinball_fwd_bwd_strided(quantile_view(pred, len(taus)), target, taus, 1.0, want_grad=True)
+        ctx.save_for_backward(dpred.as_strided(pred.shape, pred.stride()))
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (dpred,) = ctx.saved_tensors
+        return dpred * gloss, None, None
+
+
+class PinballLoss(torch.nn.Module):
+    """`loss_fn(output, y)` for a quantile model: output (B, Q * L_out, N, 1) of a TEC_MoLLM built with
+    prediction_horizon = Q * L_out, y (B, L_out, N, 1).  Takes the place of nn.HuberLoss in the reference's loop
+    (train.py:372); `TrainStep(loss=PinballLoss(taus))` runs it on the fused route."""
+
+    def __init__(self, taus):
+        super().__init__()
+        self.taus = quantile_levels(taus)
+
+    def forward(self, output: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        return PinballFn.apply(output, y, self.taus)
+
+    def extra_repr(self) -> str:
+        return f"taus={self.taus}"

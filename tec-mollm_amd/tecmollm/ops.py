@@ -631,6 +631,129 @@ def huber_fwd_bwd_strided(pred: torch.Tensor, target: torch.Tensor, delta: float
     return loss, dpred
 
 
+def _taus_array(taus):
+    ts = [float(t) for t in taus]
+    if not 1 <= len(ts) <= _lib.TECM_QUANT_MAX_Q:
+        raise ValueError(f"between 1 and {_lib.TECM_QUANT_MAX_Q} quantile levels, got {len(ts)}")
+    return (C.c_float * _lib.TECM_QUANT_MAX_Q)(*ts), len(ts)
+
+
+def pinball_fwd_bwd_strided(pred: torch.Tensor, target: torch.Tensor, taus, grad_scale: float = 1.0,
+                            want_grad: bool = True) -> Tuple[torch.Tensor, Optional[torch.Tensor], torch.Tensor]:
+    """tecm_pinball_fwd_bwd_strided (include/tecmollm.h (3k)(a)): the mean pinball loss of pred (B, Q, H, N) -- the quantile
+    view of the model's output, any strides -- against target (B, H, N) or (B, H, N, 1) at the levels `taus`, each read in
+    its own layout.  Returns (loss (1,), dpred with pred's shape AND strides -- or None --, loss_levels (Q,))."""
+    if target.dim() == 4 and target.shape[3] == 1:
+        target = target[..., 0]
+    if pred.dim() != 4 or target.dim() != 3 or (pred.shape[0], pred.shape[2], pred.shape[3]) != tuple(target.shape):
+        raise _lib.TecmError(f"pinball_fwd_bwd_strided: pred is (B, Q, H, N) and target (B, H, N), got {tuple(pred.shape)} "
+                             f"and {tuple(target.shape)}")
+    _lib.require_gpu_tensor(pred, "pred")
+    _lib.require_gpu_tensor(target, "target")
+    B, Q, H, N = pred.shape
+    tarr, nq = _taus_array(taus)
+    if nq != Q:
+        raise _lib.TecmError(f"pinball_fwd_bwd_strided: {nq} levels for a pred of {Q}")
+    if want_grad:
+        # dense and non-overlapping: sorted by stride, every dimension of more than one element steps over all the smaller ones
+        dims, span = sorted((st, sz) for st, sz in zip(pred.stride(), pred.shape) if sz > 1), 1
+        for st, sz in dims:
+            if st != span:
+                raise _lib.TecmError("pinball_fwd_bwd_strided: pred must be a dense (permuted) tensor without overlap")
+            span *= sz
+    loss = torch.empty(1, device=pred.device, dtype=torch.float32)
+    levels = torch.empty(Q, device=pred.device, dtype=torch.float32)
+    dpred = torch.empty_strided(pred.shape, pred.stride(), device=pred.device, dtype=torch.float32) if want_grad else None
+    nbx = min((B * H * N + 255) // 256, _lib.TECM_PINBALL_BLOCK_CAP)
+    ws = torch.empty(Q * nbx, device=pred.device, dtype=torch.float64)
+    p = _lib.TecmPinball(pred=pred.data_ptr(), p_stride_b=pred.stride(0), p_stride_q=pred.stride(1), p_stride_h=pred.stride(2),
+                         p_stride_n=pred.stride(3), target=target.data_ptr(), t_stride_b=target.stride(0),
+                         t_stride_h=target.stride(1), t_stride_n=target.stride(2), B=B, Q=Q, H=H, N=N, taus=tarr,
+                         grad_scale=float(grad_scale), dpred=ptr(dpred), loss_out=loss.data_ptr(),
+                         loss_levels=levels.data_ptr(), workspace=ws.data_ptr())
+    check(lib().tecm_pinball_fwd_bwd_strided(C.byref(p), stream_ptr()), "tecm_pinball_fwd_bwd_strided")
+    return loss, dpred, levels
+
+
+def _qshi(t: torch.Tensor, name: str):
+    _lib.require_gpu_tensor(t, name)
+    if t.dim() != 4:
+        raise ValueError(f"{name} must be (Q, S, H, I), got {tuple(t.shape)}")
+    return t.data_ptr(), t.stride(0), t.stride(1), t.stride(2), t.stride(3)
+
+
+def quantile_stats(levels: torch.Tensor, target: Optional[torch.Tensor], taus, stats: Optional[torch.Tensor],
+                   counts: Optional[torch.Tensor], *, adjust: Optional[torch.Tensor] = None, mean: float = 0.0,
+                   scale: float = 1.0, clip: Optional[Tuple[float, float]] = None, groups: Optional[torch.Tensor] = None,
+                   num_groups: int = 1, err_flag: int = 0, out_z: Optional[torch.Tensor] = None) -> None:
+    """tecm_quantile_stats (include/tecmollm.h (3k)(b)): one update of `stats` (G, H, 1 + Q + Q // 2, I) float64 and `counts`
+    (same shape) int32 (read as unsigned counts) from `levels` (Q, S, H, I) and `target` (S, H, I), float32 views of any
+    strides read in place.  `adjust` is a contiguous (1 or G, H, Q, I) float32 tensor added to the sorted levels; `out_z`
+    (Q, S, H, I) float32 receives them.  With `target` None only `out_z` is written (G = `num_groups`)."""
+    lp, lq, ls, lh, li = _qshi(levels, "levels")
+    Q, S, H, I = levels.shape
+    tarr, nq = _taus_array(taus)
+    if nq != Q:
+        raise ValueError(f"{nq} levels for a tensor of {Q}")
+    tp, ts, th, ti = _shi(target, (S, H, I), "target")
+    G = int(num_groups) if stats is None else stats.shape[0]
+    rows = 1 + Q + Q // 2
+    if target is not None:
+        if stats is None or stats.shape != (G, H, rows, I) or stats.dtype != torch.float64 or not stats.is_contiguous():
+            raise ValueError(f"stats must be a contiguous float64 (G, {H}, {rows}, {I}) tensor")
+        if counts is None or counts.shape != (G, H, rows, I) or counts.dtype != torch.int32 or not counts.is_contiguous():
+            raise ValueError(f"counts must be a contiguous int32 ({G}, {H}, {rows}, {I}) tensor")
+        _lib.require_gpu_tensor(stats, "stats", torch.float64)
+        _lib.require_gpu_tensor(counts, "counts", torch.int32)
+    elif out_z is None:
+        raise ValueError("without a target there must be an out_z")
+    Ga = 1
+    if adjust is not None:
+        _lib.require_gpu_tensor(adjust, "adjust")
+        Ga = adjust.shape[0]
+        if adjust.shape != (Ga, H, Q, I) or not adjust.is_contiguous() or Ga not in (1, G):
+            raise ValueError(f"adjust must be a contiguous (1 or {G}, {H}, {Q}, {I}) tensor, got {tuple(adjust.shape)}")
+    if groups is not None:
+        _lib.require_gpu_tensor(groups, "groups", torch.int32)
+        if groups.shape != (S,) or not groups.is_contiguous():
+            raise ValueError(f"groups must hold one contiguous id per sample: {tuple(groups.shape)} for {S} samples")
+    op, oq, os_, oh, oi = (None, 0, 0, 0, 0)
+    if out_z is not None:
+        if out_z.shape != (Q, S, H, I):
+            raise ValueError(f"out_z must be (Q, S, H, I) = {(Q, S, H, I)}, got {tuple(out_z.shape)}")
+        op, oq, os_, oh, oi = _qshi(out_z, "out_z")
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    c = _lib.TecmQuantileStats(levels=lp, l_stride_q=lq, l_stride_s=ls, l_stride_h=lh, l_stride_i=li, target=tp, t_stride_s=ts,
+                               t_stride_h=th, t_stride_i=ti, S=S, H=H, G=G, I=I, Q=Q, Ga=Ga, taus=tarr, mean=float(mean),
+                               scale=float(scale), clip_lo=lo, clip_hi=hi, clip=1 if clip is not None else 0,
+                               adjust=ptr(adjust), stats=ptr(stats), counts=ptr(counts), group=ptr(groups),
+                               err_flag=err_flag or None, out_z=op, o_stride_q=oq, o_stride_s=os_, o_stride_h=oh,
+                               o_stride_i=oi)
+    check(lib().tecm_quantile_stats(C.byref(c), stream_ptr()), "tecm_quantile_stats")
+
+
+def quantile_scores(levels: torch.Tensor, target: torch.Tensor, scores: torch.Tensor, row0: int, lo_idx: int, hi_idx: int, *,
+                    mean: float = 0.0, scale: float = 1.0, clip: Optional[Tuple[float, float]] = None) -> None:
+    """tecm_quantile_scores (include/tecmollm.h (3k)(c)): E = max(z_lo - y, y - z_hi) of the sorted `levels` (Q, S, H, I)
+    against `target` (S, H, I) into rows row0 .. row0 + S - 1 of the row-major float32 store `scores`, as
+    `conformal_scores` addresses it."""
+    lp, lq, ls, lh, li = _qshi(levels, "levels")
+    Q, S, H, I = levels.shape
+    tp, ts, th, ti = _shi(target, (S, H, I), "target")
+    _lib.require_gpu_tensor(scores, "scores")
+    if scores.dim() != 2 or scores.stride(1) != 1 or scores.shape[1] < H * I or not 0 <= row0 <= scores.shape[0] - S:
+        raise ValueError(f"scores must be a row-major (rows >= {row0 + S}, columns >= {H * I}) store, got {tuple(scores.shape)}")
+    if not 0 <= int(lo_idx) <= int(hi_idx) < Q:
+        raise ValueError(f"needs 0 <= lo_idx <= hi_idx < {Q}, got {(lo_idx, hi_idx)}")
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    c = _lib.TecmQuantileScores(levels=lp, l_stride_q=lq, l_stride_s=ls, l_stride_h=lh, l_stride_i=li, target=tp, t_stride_s=ts,
+                                t_stride_h=th, t_stride_i=ti, S=S, H=H, Q=Q, I=I, lo_idx=int(lo_idx), hi_idx=int(hi_idx),
+                                mean=float(mean), scale=float(scale), clip_lo=lo, clip_hi=hi,
+                                clip=1 if clip is not None else 0, scores=scores.data_ptr(),
+                                ld=scores.stride(0) if scores.shape[0] > 1 else max(scores.stride(0), H * I), row0=int(row0))
+    check(lib().tecm_quantile_scores(C.byref(c), stream_ptr()), "tecm_quantile_scores")
+
+
 def lora_fold(lB: torch.Tensor, scale: float, w_kn: Optional[torch.Tensor], w_nk: Optional[torch.Tensor], k_off: int) -> None:
     """The LoRA rows of [ W ; s B^T ] (w_kn: (k_off + r, n)) and / or the LoRA columns of [ W^T | s B ] (w_nk: (n, k_off + r))
     from lora_B (n, r); either operand fp32 or bf16, in place."""

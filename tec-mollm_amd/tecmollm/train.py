@@ -68,9 +68,15 @@ class TrainStep:
     def __init__(self, model: torch.nn.Module, lr: float = 1e-4, weight_decay: float = 1e-2, max_norm: float = 1.0,
                  accumulation_steps: int = 1, world_size: int = 1, group=None, fused_huber: bool = True,
                  optimizer: str = "native", broadcast_init: bool = True, check_divergence: bool = True,
-                 time_collective: bool = False):
+                 time_collective: bool = False, loss="huber"):
         if optimizer not in ("native", "torch"):
             raise ValueError("optimizer must be 'native' or 'torch'")
+        # loss: "huber" (the reference's HuberLoss(delta=1), every path below as before) or a PinballLoss(taus) for a
+        # quantile model (prediction_horizon = Q * L_out, include/tecmollm.h (3k))
+        from .functions import PinballLoss
+        if not (loss == "huber" if isinstance(loss, str) else isinstance(loss, PinballLoss)):
+            raise ValueError(f"loss must be 'huber' or a PinballLoss, got {loss!r}")
+        self.loss = loss
         self.model = model
         self.rank = dist.get_rank(group) if world_size > 1 else 0
         if world_size > 1 and dist.get_world_size(group) != world_size:
@@ -146,7 +152,9 @@ class TrainStep:
         if self.native:
             self.optimizer.detach_grads()              # backward hands its gradient tensors over; one add for all of them
         out = self.model(x, time_features, edge_index, edge_weight)
-        if self.native and self.fused_huber and out.dim() == 4 and out.shape[3] == 1 and out.shape == y.shape:
+        if self.loss != "huber":
+            loss = self._pinball_backward(out, y)
+        elif self.native and self.fused_huber and out.dim() == 4 and out.shape[3] == 1 and out.shape == y.shape:
             # loss and d loss / d out (already divided by accumulation_steps, train.py:78) from ONE strided kernel pair, fed
             # to autograd as the output gradient: no contiguous copies of the permuted prediction / the target, no ones_like,
             # no divide, no multiply by the upstream scalar
@@ -161,6 +169,20 @@ class TrainStep:
             self.optimizer.absorb_grads()
         return loss.detach()
 
+    def _pinball_backward(self, out: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        """The quantile model's twin of the fused Huber branch: mean pinball loss and d loss / d out (already divided by
+        accumulation_steps) from one kernel pair, fed to autograd as the output gradient."""
+        if not (self.native and self.fused_huber and out.is_cuda):
+            loss = self.loss(out, y)
+            (loss / self.accumulation_steps).backward()
+            return loss
+        from . import ops
+        from .functions import quantile_view
+        loss, dq, _ = ops.pinball_fwd_bwd_strided(quantile_view(out.detach(), len(self.loss.taus)), y, self.loss.taus,
+                                                  1.0 / self.accumulation_steps)
+        out.backward(dq.as_strided(out.shape, out.stride()))
+        return loss[0]
+
     # ------------------------------------------------------------------ recorded step (small batches)
     def step_graphed(self, x, time_features, edge_index, edge_weight, y) -> torch.Tensor:
         """`step` with the micro-batch's ~200 launches (forward, Huber loss, backward, gradient hand-over) recorded ONCE as a
@@ -171,6 +193,8 @@ class TrainStep:
         from recorded seeds PLUS one device word (`TecmDrop::seed_dev`) that the graph's first node advances.  The data-
         parallel exchange, clip + AdamW and the scheduler stay outside the graph (two launches with host scalars).
         Returns the loss tensor of the recorded step -- the SAME tensor every call; read it before the next one."""
+        if self.loss != "huber":
+            raise ValueError("step_graphed records the Huber step only; use step() with a PinballLoss")
         if not (self.native and x.is_cuda):
             raise RuntimeError("step_graphed needs the native optimizer and CUDA tensors")
         from . import devcheck, ops

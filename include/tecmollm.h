@@ -1395,6 +1395,89 @@ typedef struct {
 } TecmQuantileScores;
 int tecm_quantile_scores(const TecmQuantileScores* c, void* stream);
 
+/* (3l) forecast combination (Bates-Granger / Granger-Ramanathan): a least-squares fit, per cell (g, h, i), of the truth on
+ * M forecasts of it with an intercept.  Three steps: the moments of a fitting pass (a), the per-cell solve (b) and the blend
+ * of a batch of forecasts with fitted coefficients (c).  Everything works on the raw float32 values as the forecasts and the
+ * dataset's target hold them -- the scaled domain, BEFORE the value pipeline of (3) -- and every product and sum is float64.
+ * An operand (a member forecast, the target) is a base pointer with element strides, read in place at
+ * base[s*stride_s + h*stride_h + i*stride_i] (64-bit): the model's permuted view has stride_h = 1, stride_i = H, targets and
+ * Linear / SARIMA forecasts are node-contiguous, the mean / last baselines are stride_h = 0 views.
+ *
+ * (a) tecm_combine_moments: with z = [1, p_1 .. p_M, t] per (sample, horizon, node), a cell accumulates the upper triangle,
+ *     row-major, of the (M+2) x (M+2) matrix sum z z^T -- entry (a, b), a <= b, at k = a*(M+2) - a*(a-1)/2 + (b - a), the
+ *     first being the count n -- followed by one double `skipped`: K = (M+2)(M+3)/2 + 1 doubles.  A sample in which any
+ *     member or the target is non-finite is left out of every moment of its cell and counted in `skipped`.
+ *       stats  (G, H, K, I) doubles, ((g*H + h)*K + k)*I + i, node-contiguous as in (3b), ACCUMULATED across calls.
+ *     Ownership, order and groups as in (3b): one owning thread per cell adds its samples in ascending s in registers and
+ *     adds to `stats` once; no atomics, the same calls give the same bits, and sums of dyadic values are exact.  Cells of a
+ *     group that does not occur are neither read nor written; an id outside [0, G) skips the sample and sets
+ *     TECM_BAD_GROUP in *err_flag, never clamped.  Block shape of (3b) (lane = node, wave = horizon); an operand with
+ *     stride_h == 1 and stride_i == H goes through the padded LDS tile when 1 < H <= TECM_MAP_LDS_MAX_H, every other one is
+ *     read in place: the route does not change a bit of the result.  M is served by the compile-time bucket 1, 2, 4 or 8
+ *     (padded members contribute nothing and are not stored).
+ *     Limits: 1 <= M <= TECM_COMBINE_MAX_MEMBERS, G and ceil(H / 4) <= 65535. */
+#define TECM_COMBINE_MAX_MEMBERS 8
+typedef struct {
+  const float* base; int64_t stride_s, stride_h, stride_i;
+} TecmCombineOperand;
+typedef struct {
+  TecmCombineOperand member[TECM_COMBINE_MAX_MEMBERS];   /* the first M are read */
+  TecmCombineOperand target;
+  int64_t S; int32_t H; int32_t G; int64_t I;            /* samples, horizons, groups, nodes */
+  int32_t M; int32_t _pad;
+  double* stats;
+  const int32_t* group;          /* (S) int32; NULL: every sample in group 0 */
+  int32_t* err_flag;
+} TecmCombineMoments;
+int tecm_combine_moments(const TecmCombineMoments* c, void* stream);
+
+/* (b) tecm_combine_solve: one thread per cell of `stats`, addressed as stats[g*s_stride_g + h*s_stride_h + k*s_stride_k +
+ *     i*s_stride_i] (element strides; G*H*I cells).  With the moments of (a):
+ *       n = count,  pbar = sum p / n,  tbar = sum t / n
+ *       C_ab = sum p_a p_b - n pbar_a pbar_b,   c_a = sum p_a t - n pbar_a tbar
+ *       A = C + ridge*n*I,                      b = c + ridge*n*w0
+ *     A is factorised by Cholesky in member order.  Member m is DROPPED when A_mm <= 0 or its pivot A_mm - sum over kept
+ *     k < m of L_mk^2 is <= TECM_COMBINE_PIVOT_TOL * A_mm: it gets weight 0 and bit m of the cell's `dropped` byte, and the
+ *     kept members solve their own system.  intercept = tbar - w^T pbar.  No fused multiply-add is used, so a restatement
+ *     that performs the same operations in the same order gives the same bits.
+ *       weight (G, H, M, I) doubles, intercept (G, H, I) doubles, status (G, H, I) int32, dropped (G, H, I) uint8.
+ *     status bits: TECM_COMBINE_EMPTY (n = 0: prior weights w0, intercept 0), TECM_COMBINE_FEW (0 < n < M + 2: prior
+ *     weights, intercept tbar - w0^T pbar), TECM_COMBINE_DROPPED (at least one member dropped), TECM_COMBINE_NONFINITE (a
+ *     non-finite moment: prior weights, intercept 0; tested first).  The M buckets of (a).
+ *     Limits: 1 <= M <= TECM_COMBINE_MAX_MEMBERS, ridge >= 0, G*H*I < 2^31 * 256. */
+#define TECM_COMBINE_EMPTY 1
+#define TECM_COMBINE_FEW 2
+#define TECM_COMBINE_DROPPED 4
+#define TECM_COMBINE_NONFINITE 8
+#define TECM_COMBINE_PIVOT_TOL 1e-10
+typedef struct {
+  const double* stats; int64_t s_stride_g, s_stride_h, s_stride_k, s_stride_i;
+  int32_t G; int32_t H; int64_t I;                       /* cells: G * H * I */
+  int32_t M; int32_t _pad;
+  double ridge;
+  double w0[TECM_COMBINE_MAX_MEMBERS];                   /* the prior; the first M are read */
+  double* weight; double* intercept; int32_t* status; uint8_t* dropped;
+} TecmCombineSolve;
+int tecm_combine_solve(const TecmCombineSolve* c, void* stream);
+
+/* (c) tecm_combine_apply: out[s*o_stride_s + h*o_stride_h + i*o_stride_i] = (float)(intercept[g, h, i] + sum over m
+ *     ascending of weight[g, h, m, i] * p_m[s, h, i]), accumulated in float64 and rounded once.  The coefficients are
+ *     addressed as weight[g*w_stride_g + h*w_stride_h + m*w_stride_m + i*w_stride_i] and intercept[g*b_stride_g +
+ *     h*b_stride_h + i*b_stride_i] (element strides, any of which may be 0: pooled fits).  A non-finite member propagates.
+ *     A sample whose id is outside [0, G) gets a NaN row and sets TECM_BAD_GROUP in *err_flag.
+ *     Limits: 1 <= M <= TECM_COMBINE_MAX_MEMBERS, ceil(H / 4) <= 65535. */
+typedef struct {
+  TecmCombineOperand member[TECM_COMBINE_MAX_MEMBERS];
+  int64_t S; int32_t H; int32_t G; int64_t I;
+  int32_t M; int32_t _pad;
+  const double* weight; int64_t w_stride_g, w_stride_h, w_stride_m, w_stride_i;
+  const double* intercept; int64_t b_stride_g, b_stride_h, b_stride_i;
+  float* out; int64_t o_stride_s, o_stride_h, o_stride_i;
+  const int32_t* group;          /* (S) int32; NULL: every sample in group 0 */
+  int32_t* err_flag;
+} TecmCombineApply;
+int tecm_combine_apply(const TecmCombineApply* c, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

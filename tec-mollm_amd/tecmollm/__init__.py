@@ -6,7 +6,7 @@ Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
                    input attribution, ensemble forecasts and their scores, spatial and temporal attention maps, conformal
                    prediction intervals, significance of the comparison (block bootstrap, Diebold-Mariano), event verification
                    (contingency scores, Brier, ROC, FSS), quantile forecasts (pinball-loss training, quantile scores,
-                   conformalized quantile regression), raw-data preprocessing
+                   conformalized quantile regression), forecast combination (per-cell stacking weights), raw-data preprocessing
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/features/    mirror of the reference's feature engineering (`from src.features.feature_engineering import ...`)
   src/data/        mirrors of the reference's dataset and data loader, and the series-backed SeriesWindowDataset
@@ -34,6 +34,8 @@ from .events import EventThresholds, evaluate_events, target_slots, write_events
 from . import quantile  # noqa: F401
 from .quantile import (CQRIntervals, QuantileModel, calibrate_cqr, evaluate_quantiles, quantile_config,  # noqa: F401
                        quantile_forecast, write_quantiles)
+from . import combine  # noqa: F401
+from .combine import Combination, CombinationMoments, fit_combination, write_combination  # noqa: F401
 from . import preprocess  # noqa: F401
 from .preprocess import DeviceStandardScaler, preprocess_splits  # noqa: F401
 
@@ -47,4 +49,5 @@ __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradien
            "preprocess_splits", "significance", "WindowScores", "score_windows", "block_bootstrap", "bootstrap_intervals",
            "diebold_mariano", "evaluate_significance", "write_significance", "events", "EventThresholds", "target_slots",
            "evaluate_events", "write_events", "quantile", "PinballFn", "PinballLoss", "QuantileModel", "CQRIntervals",
-           "quantile_config", "quantile_forecast", "evaluate_quantiles", "calibrate_cqr", "write_quantiles"]
+           "quantile_config", "quantile_forecast", "evaluate_quantiles", "calibrate_cqr", "write_quantiles", "combine", "Combination",
+           "CombinationMoments", "fit_combination", "write_combination"]

@@ -240,6 +240,48 @@ class TecmQuantileScores(C.Structure):
     ]
 
 
+TECM_COMBINE_MAX_MEMBERS = 8
+TECM_COMBINE_EMPTY, TECM_COMBINE_FEW, TECM_COMBINE_DROPPED, TECM_COMBINE_NONFINITE = 1, 2, 4, 8
+TECM_COMBINE_PIVOT_TOL = 1e-10
+
+
+class TecmCombineOperand(C.Structure):
+    _fields_ = [("base", c_f32p), ("stride_s", C.c_int64), ("stride_h", C.c_int64), ("stride_i", C.c_int64)]
+
+
+class TecmCombineMoments(C.Structure):
+    _fields_ = [
+        ("member", TecmCombineOperand * TECM_COMBINE_MAX_MEMBERS), ("target", TecmCombineOperand),
+        ("S", C.c_int64), ("H", C.c_int32), ("G", C.c_int32), ("I", C.c_int64),
+        ("M", C.c_int32), ("_pad", C.c_int32),
+        ("stats", C.c_void_p), ("group", C.c_void_p), ("err_flag", C.c_void_p),
+    ]
+
+
+class TecmCombineSolve(C.Structure):
+    _fields_ = [
+        ("stats", C.c_void_p), ("s_stride_g", C.c_int64), ("s_stride_h", C.c_int64), ("s_stride_k", C.c_int64),
+        ("s_stride_i", C.c_int64),
+        ("G", C.c_int32), ("H", C.c_int32), ("I", C.c_int64),
+        ("M", C.c_int32), ("_pad", C.c_int32),
+        ("ridge", C.c_double), ("w0", C.c_double * TECM_COMBINE_MAX_MEMBERS),
+        ("weight", C.c_void_p), ("intercept", C.c_void_p), ("status", C.c_void_p), ("dropped", C.c_void_p),
+    ]
+
+
+class TecmCombineApply(C.Structure):
+    _fields_ = [
+        ("member", TecmCombineOperand * TECM_COMBINE_MAX_MEMBERS),
+        ("S", C.c_int64), ("H", C.c_int32), ("G", C.c_int32), ("I", C.c_int64),
+        ("M", C.c_int32), ("_pad", C.c_int32),
+        ("weight", C.c_void_p), ("w_stride_g", C.c_int64), ("w_stride_h", C.c_int64), ("w_stride_m", C.c_int64),
+        ("w_stride_i", C.c_int64),
+        ("intercept", C.c_void_p), ("b_stride_g", C.c_int64), ("b_stride_h", C.c_int64), ("b_stride_i", C.c_int64),
+        ("out", c_f32p), ("o_stride_s", C.c_int64), ("o_stride_h", C.c_int64), ("o_stride_i", C.c_int64),
+        ("group", C.c_void_p), ("err_flag", C.c_void_p),
+    ]
+
+
 class TecmMetricsWindow(C.Structure):
     _fields_ = [
         ("pred", c_f32p), ("p_stride_s", C.c_int64), ("p_stride_h", C.c_int64), ("p_stride_i", C.c_int64),
@@ -550,6 +592,9 @@ EXPORTS = {
     "tecm_pinball_fwd_bwd_strided": (C.c_int, [C.POINTER(TecmPinball), C.c_void_p]),
     "tecm_quantile_stats": (C.c_int, [C.POINTER(TecmQuantileStats), C.c_void_p]),
     "tecm_quantile_scores": (C.c_int, [C.POINTER(TecmQuantileScores), C.c_void_p]),
+    "tecm_combine_moments": (C.c_int, [C.POINTER(TecmCombineMoments), C.c_void_p]),
+    "tecm_combine_solve": (C.c_int, [C.POINTER(TecmCombineSolve), C.c_void_p]),
+    "tecm_combine_apply": (C.c_int, [C.POINTER(TecmCombineApply), C.c_void_p]),
     "tecm_metrics_window": (C.c_int, [C.POINTER(TecmMetricsWindow), C.c_void_p]),
     "tecm_block_bootstrap": (C.c_int, [C.POINTER(TecmBlockBootstrap), C.c_void_p]),
     "tecm_window_batch": (C.c_int, [C.POINTER(TecmWindowBatch), C.c_void_p]),

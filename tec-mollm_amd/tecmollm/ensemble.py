@@ -23,7 +23,7 @@ import torch
 from . import ops
 from .devcheck import check_device_errors
 from .functions import dropout_seed
-from .evaluate import MODEL_NAME, baseline_forecast, baseline_name, check_grid
+from .evaluate import MODEL_NAME, baseline_names, batch_forecasts, check_grid
 from .loop import _batches
 
 MC_NAME = "TEC-MoLLM-MC"
@@ -142,7 +142,7 @@ def evaluate_ensemble(model_or_models, dataset, edge_index: torch.Tensor, batch_
     if groups is not None and (groups.dtype != torch.int32 or groups.shape != (len(dataset),)):
         raise ValueError(f"groups must be an int32 tensor with one id per dataset index ({len(dataset)})")
     kinds = list(baselines)
-    base_names = [baseline_name(k) for k in kinds]
+    base_names = baseline_names(kinds, groups, num_groups, "evaluate_ensemble")
     models = _models(model_or_models)
     K = _member_count(model_or_models, members)
     first = model_or_models if models is None else models[0]
@@ -165,7 +165,7 @@ def evaluate_ensemble(model_or_models, dataset, edge_index: torch.Tensor, batch_
             ids = groups[torch.as_tensor(chunk, dtype=torch.int64).to(groups.device, non_blocking=True)]
         mem = ensemble_members(model_or_models, x, tf, edge_index, members, seed, int(first_chunk) + ordinal, edge_weight)
         mean_raw = em.update(mem, y, ids, outputs=("mean_raw",))["mean_raw"]
-        forecasts = [(MODEL_NAME, out)] + [(name, baseline_forecast(dataset, chunk, k)) for name, k in zip(base_names, kinds)]
+        forecasts = batch_forecasts(dataset, chunk, out, base_names, kinds, ids)
         forecasts.append((MC_NAME, mean_raw.unsqueeze(-1)))
         for name, pred in forecasts:
             hms[name].update(pred, y)

@@ -40,11 +40,13 @@ LINEAR_NAME = "Linear"      # a fitted src.models.baselines.LinearBaseline, like
 
 
 def baseline_name(kind) -> str:
-    """The result-dict name of one element of `baselines=`: a kind string of `KINDS`, or a fitted `SarimaBaseline` or
-    `LinearBaseline`."""
+    """The result-dict name of one element of `baselines=`: a kind string of `KINDS`, a fitted `SarimaBaseline` or
+    `LinearBaseline`, or a fitted `tecmollm.combine.Combination` (its own `name`)."""
     if isinstance(kind, str):
         if kind in KINDS:
             return NAMES[kind]
+    elif _is_combination(kind):
+        return kind.name
     else:
         from src.models.baselines import LinearBaseline, SarimaBaseline
         for cls, name in ((SarimaBaseline, SARIMA_NAME), (LinearBaseline, LINEAR_NAME)):
@@ -58,6 +60,35 @@ def baseline_name(kind) -> str:
 def baseline_forecast(dataset, indices: Sequence[int], kind) -> torch.Tensor:
     """The (B, L_out, N, 1) forecast of one element of `baselines=` for the windows `indices`."""
     return window_baseline(dataset, indices, kind) if isinstance(kind, str) else kind.forecast_windows(dataset, indices)
+
+
+def _is_combination(kind) -> bool:
+    from .combine import Combination
+    return isinstance(kind, Combination)
+
+
+def baseline_names(baselines, groups=None, num_groups=None, where: str = "this evaluation") -> list:
+    """The result-dict names of `baselines=`.  A `Combination` among them must not share its name with another entry, and
+    one fitted with more than one group needs the evaluation's `groups` / `num_groups` to match: ValueError otherwise."""
+    kinds = list(baselines)
+    names = [baseline_name(k) for k in kinds]
+    for k, name in zip(kinds, names):
+        if _is_combination(k):
+            if ([MODEL_NAME] + names).count(name) > 1:
+                raise ValueError(f"the name {name!r} of a combination collides with another entry of {[MODEL_NAME] + names}")
+            k._check_groups(groups, num_groups, where)
+    return names
+
+
+def batch_forecasts(dataset, chunk, out: torch.Tensor, names, kinds, ids=None) -> list:
+    """The forecasts a batch is scored on, [(name, (B, L_out, N, 1) tensor)]: the model's output `out`, then `baselines=` in
+    the order given.  Plain members are evaluated first; a `Combination` is then handed the model's output and those of its
+    members that are themselves listed, and computes the others for itself alone."""
+    preds = [None if _is_combination(k) else baseline_forecast(dataset, chunk, k) for k in kinds]
+    if any(p is None for p in preds):
+        computed = [(k, p) for k, p in zip(kinds, preds) if p is not None]
+        preds = [k.forecast_batch(dataset, chunk, out, ids, computed) if p is None else p for k, p in zip(kinds, preds)]
+    return [(MODEL_NAME, out)] + list(zip(names, preds))
 
 
 def _launch(dataset, indices: Sequence[int], kind: str, channel: int, period: int, L_out: int, out: torch.Tensor,
@@ -125,7 +156,7 @@ def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_
     Returns ({name: HorizonMetrics}, {name: MapMetrics})."""
     from src.evaluation.metrics import HorizonMetrics, MapMetrics
     kinds = list(baselines)
-    names = [baseline_name(k) for k in kinds]
+    names = baseline_names(kinds, groups, num_groups, "the evaluation")
     model.eval()
     hms: Dict[str, HorizonMetrics] = {}
     mms: Dict[str, MapMetrics] = {}
@@ -140,7 +171,7 @@ def _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_
         ids = None
         if mms and groups is not None:
             ids = groups[torch.as_tensor(chunk, dtype=torch.int64).to(groups.device, non_blocking=True)]
-        forecasts = [(MODEL_NAME, out)] + [(name, baseline_forecast(dataset, chunk, k)) for name, k in zip(names, kinds)]
+        forecasts = batch_forecasts(dataset, chunk, out, names, kinds, ids)
         for name, pred in forecasts:
             hms[name].update(pred, y)
             if mms:
@@ -162,7 +193,9 @@ def evaluate_split(model: torch.nn.Module, dataset, edge_index: torch.Tensor, ba
     One pass over the batches: the model's output and each baseline's stride-0 view are fed in place to a
     `HorizonMetrics` of their own, with no host synchronisation per batch.  An element of `baselines` is a kind string of
     `window_baseline`, a fitted `src.models.baselines.SarimaBaseline`, whose entry is named "SARIMA" (one
-    `tecm_sar_forecast` launch per batch), or a fitted `LinearBaseline`, named "Linear" (one `tecm_lin_forecast` launch); the same holds for `evaluate_maps` and `evaluate_ensemble`.  `order` and `group` as in `loop.validate`:
+    `tecm_sar_forecast` launch per batch), a fitted `LinearBaseline`, named "Linear" (one `tecm_lin_forecast` launch), or a
+    fitted `tecmollm.combine.Combination`, named by its `name` (one `tecm_combine_apply` launch on the model's output and the
+    member forecasts of the batch; one fitted with several groups needs `evaluate_maps`' groups); the same holds for `evaluate_maps` and `evaluate_ensemble`.  `order` and `group` as in `loop.validate`:
     a rank evaluates its shard and every rank returns the metrics of the whole split."""
     hms, _ = _score_pass(model, dataset, edge_index, batch_size, scaler, baselines, edge_weight, order, None, None)
     if not hms:

@@ -1295,6 +1295,59 @@ typedef struct {
 } TecmLinForecast;
 int tecm_lin_forecast(const TecmLinForecast* f, void* stream);
 
+/* (10) AnalogBaseline (not in the reference): the analog ensemble, the non-parametric baseline of space-weather and NWP
+ * post-processing.  For every (query window, node) the K stretches of the node's training record that lie nearest to the
+ * query's last m input steps are found, and what followed them is the forecast: K members, and their mean.
+ *   archive     A (N, Ta) fp32 NODE-MAJOR: A[n*Ta + r] is the feature-scaled channel of node n at row r.  The outcomes are
+ *               read by tecm_analog_forecast from Y (N, Ty), node-major too, whose row r is the same instant as row r of A.
+ *   candidates  a start row c of a segment A[c .. c+m-1]; its origin is o_c = c + m and its outcome Y[o_c + h], h < L_out.
+ *               Valid: 0 <= c, c + m <= Ta, c + m + L_out <= Ty.
+ *   queries     window b starts at row a = starts[b] of Xq (Tq, N*C) (time-major, as a dataset holds it); its segment is
+ *               Xq[(a + L_in - m + l)*N*C + n*C + channel], l < m, and its origin o_q = a + L_in + origin_shift (the shift
+ *               maps a row of Xq to the archive's row numbering; it only enters the exclusion rule).
+ *   distance    d = sum_{l<m} (A[c+l] - q[l])^2 in fp32, every term rounded (difference, fused multiply-add).  A candidate
+ *               whose d is NaN or +inf is never selected, so a query segment that holds a NaN selects nothing.
+ *   admission   keys (key_arch (Tk) and key_q (S) int32, both or neither): only candidates with key_arch[o_c] == key_q[b];
+ *               needs Tk > the last candidate's origin.  exclude > 0: only candidates with |o_c - o_q| >= exclude.
+ *   selection   the K admitted candidates smallest by (d, c) -- on equal distance the earlier row -- ascending in that order:
+ *               idx (S, N, K) int32, dist (S, N, K) fp32, unused places -1 / +inf, count (S, N) int32 = min(K, admitted).
+ * The order (d, c) is total, so the result does not depend on the launch geometry and two calls return identical bits.
+ * A block owns (one node, a tile of queries) and sweeps the node's archive in chunks staged in LDS; the distances are never
+ * stored.  tecm_analog_search_supported is pure host arithmetic: 1 when the descriptor's shape is served (no pointer is
+ * followed; key_arch != NULL says that keys are in use, which Tk must then cover), else 0 with the reason in tecm_last_error; chunk / query_tile / n_candidates (each may be NULL) receive the
+ * candidates per staged chunk, the queries per block and the number of valid candidates.  Windows are range-checked on the
+ * host when starts_host_check is given; a window outside [0, Tq - L_in] that reaches the kernel selects nothing. */
+enum { TECM_ANALOG_MAX_K = 32, TECM_ANALOG_MAX_M = 512, TECM_ANALOG_MAX_H = 32 };
+typedef struct {
+  const float* A; int64_t Ta;                   /* (N, Ta) node-major */
+  int64_t Ty;                                   /* rows of the outcome series: bounds the candidates */
+  const float* Xq; int64_t Tq;                  /* (Tq, N*C) */
+  const int64_t* starts; const int64_t* starts_host_check;
+  int64_t origin_shift;
+  int32_t N, C, channel, L_in, L_out, m, K, S;
+  const int32_t* key_arch; int64_t Tk;          /* NULL: no keys */
+  const int32_t* key_q;
+  int32_t exclude, _pad;                        /* 0: no exclusion */
+  int32_t* idx; float* dist; int32_t* count;
+} TecmAnalogSearch;
+int tecm_analog_search_supported(const TecmAnalogSearch* s, int32_t* chunk, int32_t* query_tile, int64_t* n_candidates);
+int tecm_analog_search(const TecmAnalogSearch* s, void* stream);
+
+/* tecm_analog_forecast: from idx / count as tecm_analog_search wrote them (B = S windows) and the outcomes Y (N, Ty):
+ *   members[((k*B + b)*L_out + h)*N + n] = Y[n*Ty + idx[b,n,k] + m + h] for k < count[b,n], NaN for the others
+ *                                          (K, B, L_out, N) contiguous, the layout of the ensemble statistics (3d)
+ *   out[b*o_stride_b + h*o_stride_h + n*o_stride_n] = (float)(fp64 sum of the count members, k ascending, / count),
+ *                                          NaN where count == 0; a NaN outcome propagates
+ * Either output may be NULL.  An index whose outcome row would leave the Ty rows is not read and counts as NaN. */
+typedef struct {
+  const float* Y; int64_t Ty;                   /* (N, Ty) node-major */
+  const int32_t* idx; const int32_t* count;
+  int32_t N, K, m, L_out, B, _pad;
+  float* out; int64_t o_stride_b, o_stride_h, o_stride_n;
+  float* members;
+} TecmAnalogForecast;
+int tecm_analog_forecast(const TecmAnalogForecast* f, void* stream);
+
 /* (3k) quantile forecasts: the pinball loss a quantile model is trained with (a), the scores a Q-level forecast is judged
  * by per cell (g, h, i) (b), and the nonconformity score of conformalized quantile regression (c).
  *

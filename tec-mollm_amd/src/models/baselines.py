@@ -22,18 +22,24 @@ consistent but not the maximum-likelihood ones: expect coefficients and forecast
 by ridge regression against the TARGET-scaled series -- the "Linear" baseline an LLM-based forecaster is asked to beat.
 The normal equations of every window of a split are accumulated on the device (`tecm_lin_gram`), solved by Cholesky
 (`tecm_lin_solve`), and every window of a test split is forecast by one launch (`tecm_lin_forecast`).
+
+`AnalogBaseline` is not in the reference either: the analog ensemble, the non-parametric baseline.  For every window and
+node the K stretches of the training record nearest to the window's last input steps are searched on the device
+(`tecm_analog_search`: the distances are swept and the K best kept in one kernel, no table is stored), and what followed
+them is the forecast (`tecm_analog_forecast`): K members, whose spread comes from the data, and their mean.
 """
 from __future__ import annotations
 
 import ctypes as C
 import logging
+import weakref
 from typing import Sequence, Union
 
 import numpy as np
 import torch
 
 from tecmollm import _lib
-from tecmollm._lib import (TecmLinForecast, TecmLinGram, TecmLinSolve, TecmSarFit, TecmSarForecast, TecmSlotMean,
+from tecmollm._lib import (TecmAnalogForecast, TecmAnalogSearch, TecmLinForecast, TecmLinGram, TecmLinSolve, TecmSarFit, TecmSarForecast, TecmSlotMean,
                            TecmWindowBaseline, check, lib, require_gpu_tensor, stream_ptr)
 
 log = logging.getLogger(__name__)
@@ -579,6 +585,345 @@ class LinearBaseline:
             raise ValueError(f"fitted for {self.H_} horizons, asked for {steps} steps")
         tail = torch.as_tensor(self.tail_).to(self.device).contiguous()
         out = self.forecast_series(tail, [0], self.L_in_, self.H_).cpu().numpy().astype(np.float64)
+        return {int(n): out[0, :int(steps), int(n)] for n in node_indices if 0 <= int(n) < self.num_nodes_}
+
+
+# ------------------------------------------------------------------------------------ AnalogBaseline
+ANALOG_DEFAULT_MATCH = LINEAR_DEFAULT_LAGS
+ANALOG_NO_KEY = -1           # the key of an archive row that admits no query (no time feature, no condition, a negative id)
+
+
+def analog_limits(k, match_len, L_in, L_out=1):
+    """Checks K, m and L_out against what the kernels serve and returns (K, m): `match_len` None is min(L_in, 48).
+    ValueError naming the argument otherwise."""
+    k = int(k)
+    if not 1 <= k <= _lib.TECM_ANALOG_MAX_K:
+        raise ValueError(f"k must lie in [1, {_lib.TECM_ANALOG_MAX_K}], got {k}")
+    L_in = int(L_in)
+    m = min(L_in, ANALOG_DEFAULT_MATCH) if match_len is None else int(match_len)
+    if not 1 <= m <= min(L_in, _lib.TECM_ANALOG_MAX_M):
+        raise ValueError(f"match_len must lie in [1, min(L_in, {_lib.TECM_ANALOG_MAX_M})] (L_in = {L_in}), got {m}")
+    if not 1 <= int(L_out) <= _lib.TECM_ANALOG_MAX_H:
+        raise ValueError(f"L_out must lie in [1, {_lib.TECM_ANALOG_MAX_H}], got {L_out}")
+    return k, m
+
+
+def _search_desc(Ta, Ty, Tq, N, Cc, channel, L_in, L_out, m, K, S, exclude=0, Tk=0, origin_shift=0) -> TecmAnalogSearch:
+    return TecmAnalogSearch(Ta=int(Ta), Ty=int(Ty), Tq=int(Tq), N=int(N), C=int(Cc), channel=int(channel), L_in=int(L_in),
+                            L_out=int(L_out), m=int(m), K=int(K), S=int(S), exclude=int(exclude), Tk=int(Tk),
+                            origin_shift=int(origin_shift))
+
+
+def analog_search_geometry(Ta, Ty, Tq, N, Cc, channel, L_in, L_out, m, K, S):
+    """(candidates per staged chunk, queries per block, valid candidates) of the `tecm_analog_search` launch for this shape,
+    asked of the library (pure host arithmetic: no GPU needed); ValueError with the library's reason when it is not served."""
+    chunk, tile, ncand = C.c_int32(), C.c_int32(), C.c_int64()
+    desc = _search_desc(Ta, Ty, Tq, N, Cc, channel, L_in, L_out, m, K, S)
+    if not lib().tecm_analog_search_supported(C.byref(desc), C.byref(chunk), C.byref(tile), C.byref(ncand)):
+        raise ValueError(lib().tecm_last_error().decode("utf-8", "replace"))
+    return chunk.value, tile.value, ncand.value
+
+
+def _require_device(t, name: str, dtype, shape=None, contiguous=True) -> None:
+    """ValueError naming `name` unless `t` is a device tensor of `dtype` (and `shape`, and contiguous)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{name} must be a tensor on the GPU; the HIP path has no CPU fallback")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if contiguous and not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def analog_search(A: torch.Tensor, Ty: int, Xq: torch.Tensor, starts: Sequence[int], L_in: int, L_out: int, m: int, K: int,
+                  channel: int = 0, key_arch: torch.Tensor = None, key_q: torch.Tensor = None, exclude: int = 0,
+                  origin_shift: int = 0, host_check: bool = True):
+    """The K nearest archive segments of every (window, node): A (N, Ta) node-major and Xq (Tq, N, C), contiguous float32
+    device tensors; `starts` the windows' first rows in Xq; `Ty` the rows of the outcome series (it bounds the
+    candidates).  `key_arch` (Tk) and `key_q` (S) int32 device tensors admit only candidates whose origin row carries
+    the query's key; `exclude` > 0 refuses candidates whose origin lies nearer than that to the query's, which is
+    `start + L_in + origin_shift` in archive rows.  Returns (idx (S, N, K) int32, dist (S, N, K) float32, count (S, N)
+    int32) on the device: ascending by (dist, idx), unused places -1 / +inf."""
+    _require_device(A, "archive", torch.float32)
+    _require_device(Xq, "X", torch.float32)
+    if A.dim() != 2:
+        raise ValueError(f"archive must be (N, Ta) node-major, got {tuple(A.shape)}")
+    if Xq.dim() != 3:
+        raise ValueError(f"X must be (T, N, C), got {tuple(Xq.shape)}")
+    N, Ta = A.shape
+    Tq, Nq, Cc = Xq.shape
+    if Nq != N:
+        raise ValueError(f"num_nodes: the archive holds {N} nodes, the query dataset {Nq}")
+    host = torch.tensor([int(a) for a in starts], dtype=torch.int64)
+    S = host.numel()
+    if S == 0:
+        raise ValueError("analog_search() needs at least one window")
+    if (key_arch is None) != (key_q is None):
+        raise ValueError("key_arch and key_q must be given together")
+    Tk = 0
+    if key_arch is not None:
+        _require_device(key_arch, "key_arch", torch.int32)
+        _require_device(key_q, "key_q", torch.int32, (S,))
+        Tk = key_arch.numel()
+    desc = _search_desc(Ta, Ty, Tq, N, Cc, channel, L_in, L_out, m, K, S, exclude, Tk, origin_shift)
+    if key_arch is not None:
+        desc.key_arch, desc.key_q = key_arch.data_ptr(), key_q.data_ptr()
+    if not lib().tecm_analog_search_supported(C.byref(desc), None, None, None):
+        raise ValueError(lib().tecm_last_error().decode("utf-8", "replace"))
+    idx = torch.empty(S, N, int(K), device=A.device, dtype=torch.int32)
+    dist = torch.empty(S, N, int(K), device=A.device, dtype=torch.float32)
+    count = torch.empty(S, N, device=A.device, dtype=torch.int32)
+    dev_starts = host.to(A.device, non_blocking=True)
+    desc.A, desc.Xq, desc.starts = A.data_ptr(), Xq.data_ptr(), dev_starts.data_ptr()
+    desc.starts_host_check = host.data_ptr() if host_check else None
+    desc.idx, desc.dist, desc.count = idx.data_ptr(), dist.data_ptr(), count.data_ptr()
+    check(lib().tecm_analog_search(C.byref(desc), stream_ptr()), "tecm_analog_search")
+    return idx, dist, count
+
+
+def analog_forecast(Y: torch.Tensor, idx: torch.Tensor, count: torch.Tensor, m: int, L_out: int, out: torch.Tensor = None,
+                    want_mean: bool = True, want_members: bool = False):
+    """From the outcomes Y (N, Ty) node-major and a search result: (mean (B, L_out, N) float32 or None, members (K, B, L_out,
+    N) float32 or None).  `out` (B, L_out, N), any strides, receives the mean in place."""
+    _require_device(Y, "outcomes", torch.float32)
+    _require_device(idx, "idx", torch.int32)
+    if Y.dim() != 2 or idx.dim() != 3 or idx.shape[1] != Y.shape[0]:
+        raise ValueError(f"outcomes must be (N, Ty) and idx (B, N, K), got {tuple(Y.shape)} and {tuple(idx.shape)}")
+    B, N, K = idx.shape
+    _require_device(count, "count", torch.int32, (B, N))
+    L_out = int(L_out)
+    if out is None and want_mean:
+        out = torch.empty(B, L_out, N, device=Y.device, dtype=torch.float32)
+    if out is not None:
+        _require_device(out, "out", torch.float32, (B, L_out, N), contiguous=False)
+    members = torch.empty(K, B, L_out, N, device=Y.device, dtype=torch.float32) if want_members else None
+    f = TecmAnalogForecast(Y=Y.data_ptr(), Ty=Y.shape[1], idx=idx.data_ptr(), count=count.data_ptr(), N=N, K=K, m=int(m),
+                           L_out=L_out, B=B, out=None if out is None else out.data_ptr(),
+                           o_stride_b=0 if out is None else out.stride(0),
+                           o_stride_h=0 if out is None else (out.stride(1) if L_out > 1 else 1),
+                           o_stride_n=0 if out is None else out.stride(2), members=None if members is None else members.data_ptr())
+    check(lib().tecm_analog_forecast(C.byref(f), stream_ptr()), "tecm_analog_forecast")
+    return out, members
+
+
+class AnalogBaseline:
+    """The analog ensemble (AnEn): for every (window, node) the `k` stretches of the training record that lie nearest, in
+    squared distance over the last `match_len` input steps of `channel` (None: min(L_in, 48)), to the window's own, and
+    what followed them -- `k` members whose plain mean is the point forecast.  Non-parametric: `fit` only stores the record.
+
+    Admission.  `same_slot` (default) admits only stretches whose forecast origin falls in the query's time-of-day slot
+    (`time_features[origin, 0]`); `condition=` of `fit` and of the query methods adds a group id, e.g. the storm level of
+    `window_groups_by_index`: an int32 id per row of the dataset's X, or per sample of the dataset (mapped to the sample's
+    origin row; the other rows then admit nothing).  A negative id admits nothing.  An archive row without a time feature
+    (the row just past X when the target series is longer) admits nothing while keys are in use.  When the query dataset
+    is the object the baseline was fitted on, stretches whose origin lies nearer than `exclude` rows to the query's are
+    refused (None: match_len + L_out, so that neither segment nor outcome overlaps the query's targets).
+
+    What it is not: one channel only, matched per node (no whole-map analog date), uniform weights, and the outcomes are
+    taken as they are (no adjustment of their level to the query's).
+
+    After `fit`: `n_candidates_`, `match_len_`, `H_` (the dataset's L_out), `num_nodes_`, `row0_` (the first dataset row
+    of the archive).  The archive and its outcomes live on the device node-major, 2 * N * Ta * 4 bytes together (408 MB at
+    N = 2911 and Ta = 17 520, four years of 2-hour maps); pickling copies them to numpy (`archive_`,
+    `outcomes_`) and the device tensors are rebuilt on first use."""
+
+    _DEVICE_STATE = ("_A_dev", "_Y_dev", "_keys_dev", "_fit_ref")
+
+    def __init__(self, k: int = 16, match_len=None, channel: int = 0, same_slot: bool = True, exclude=None,
+                 device: Union[str, torch.device] = "cuda"):
+        analog_limits(k, match_len, _lib.TECM_ANALOG_MAX_M if match_len is None else max(int(match_len), 1))
+        if int(channel) < 0:
+            raise ValueError(f"channel must not be negative, got {channel}")
+        if exclude is not None and int(exclude) < 0:
+            raise ValueError(f"exclude must not be negative, got {exclude}")
+        self.k, self.match_len, self.channel = int(k), None if match_len is None else int(match_len), int(channel)
+        self.same_slot, self.exclude, self.device = bool(same_slot), None if exclude is None else int(exclude), torch.device(device)
+        self.n_candidates_ = self.match_len_ = self.H_ = self.num_nodes_ = self.row0_ = self.L_in_ = None
+        self.archive_ = self.outcomes_ = self.slot_ = self.cond_ = None
+        self._A_dev = self._Y_dev = self._keys_dev = self._fit_ref = None
+
+    # joblib / pickle: numpy only
+    def __getstate__(self):
+        state = {k: v for k, v in self.__dict__.items() if k not in self._DEVICE_STATE}
+        if self._A_dev is not None and self.archive_ is None:
+            state["archive_"], state["outcomes_"] = self._A_dev.cpu().numpy(), self._Y_dev.cpu().numpy()
+        state["device"] = str(self.device)
+        return state
+
+    def __setstate__(self, state):
+        self.__dict__.update(state)
+        self.device = torch.device(state["device"])
+        self._A_dev = self._Y_dev = self._keys_dev = self._fit_ref = None
+
+    # ---- keys
+    @staticmethod
+    def _condition_rows(condition, dataset, rows: int):
+        """`condition` -> an int32 numpy id per row 0 .. rows - 1 of the dataset's series (ANALOG_NO_KEY where none is given)."""
+        cond = condition.cpu().numpy() if isinstance(condition, torch.Tensor) else np.asarray(condition)
+        if cond.ndim != 1 or not np.issubdtype(cond.dtype, np.integer):
+            raise ValueError("condition must be a 1-D integer array")
+        origins = np.asarray(dataset.sample_indices, dtype=np.int64) + dataset.L_in
+        out = np.full(max(rows, int(origins.max()) + 1 if origins.size else 0), ANALOG_NO_KEY, dtype=np.int64)
+        if cond.shape[0] == dataset.X.shape[0]:
+            out[:cond.shape[0]] = cond[:out.shape[0]]
+        elif cond.shape[0] == dataset.num_samples:
+            out[origins] = cond
+        else:
+            raise ValueError(f"condition must hold one id per row of X ({dataset.X.shape[0]}) or per sample ({dataset.num_samples}), "
+                             f"got {cond.shape[0]}")
+        out[out < 0] = ANALOG_NO_KEY
+        return out[:rows].astype(np.int32)
+
+    @staticmethod
+    def _slot_rows(dataset, rows: int):
+        tf = dataset.time_features[:, 0].to(torch.int32).cpu().numpy()
+        out = np.full(rows, ANALOG_NO_KEY, dtype=np.int32)
+        out[:min(rows, tf.shape[0])] = tf[:rows]
+        return out
+
+    @staticmethod
+    def _combine(slot, cond):
+        """key = cond * 12 + slot; ANALOG_NO_KEY where either is; None when neither rule is in use."""
+        if slot is None and cond is None:
+            return None
+        if cond is None:
+            return slot
+        if slot is None:
+            return cond
+        key = cond.astype(np.int64) * SLOTS_PER_DAY + slot
+        key[(slot < 0) | (cond < 0)] = ANALOG_NO_KEY
+        return key.astype(np.int32)
+
+    def fit(self, dataset, indices=None, condition=None) -> "AnalogBaseline":
+        """Stores the record behind every sample of a `SlidingWindowSamplerDataset` or `SeriesWindowDataset`, or behind the
+        samples `indices` (a range-like progression; the archive is the stretch of rows from the first sample's first
+        input to the last sample's last target)."""
+        first, step, count = _progression(indices, dataset.num_samples)
+        T, Hh, W, Cc = dataset.X.shape
+        N = Hh * W
+        if not 0 <= self.channel < Cc:
+            raise ValueError(f"channel {self.channel} lies outside [0, {Cc})")
+        K, m = analog_limits(self.k, self.match_len, dataset.L_in, dataset.L_out)
+        if "Ys" in dataset.__dict__:
+            ys = dataset.Ys.view(dataset.Ys.shape[0], N)
+        else:
+            ys = rebuilt_target_series(dataset.Y.view(dataset.Y.shape[0], N, dataset.Y.shape[3]))
+        row0 = dataset.sample_indices[first]
+        last = dataset.sample_indices[first + (count - 1) * step]
+        Ta, Ty = min(last + dataset.L_in, T) - row0, min(last + dataset.L_in + dataset.L_out, ys.shape[0]) - row0
+        log.info("Storing the analog archive (%d rows, %d nodes)...", Ta, N)
+        self._A_dev = dataset.X.view(T, N, Cc)[row0:row0 + Ta, :, self.channel].t().contiguous()
+        self._Y_dev = ys[row0:row0 + Ty].t().contiguous()
+        self.archive_ = self.outcomes_ = None
+        self.slot_ = self._slot_rows(dataset, row0 + Ta + 1)[row0:] if self.same_slot else None
+        self.cond_ = None if condition is None else self._condition_rows(condition, dataset, row0 + Ta + 1)[row0:]
+        self._keys_dev = None
+        _, _, ncand = analog_search_geometry(Ta, Ty, dataset.L_in, N, 1, 0, dataset.L_in, dataset.L_out, m, K, 1)
+        self.n_candidates_, self.match_len_, self.H_, self.num_nodes_, self.row0_, self.L_in_ = int(ncand), m, dataset.L_out, N, int(row0), dataset.L_in
+        self._fit_ref = weakref.ref(dataset)
+        return self
+
+    def _require_fitted(self):
+        if self.n_candidates_ is None:
+            raise ValueError("AnalogBaseline used before fit()")
+
+    def _archive_on(self, device):
+        self._require_fitted()
+        if self._A_dev is None or self._A_dev.device != device:
+            if self.archive_ is None:
+                self.archive_, self.outcomes_ = self._A_dev.cpu().numpy(), self._Y_dev.cpu().numpy()
+            self._A_dev = torch.as_tensor(self.archive_).to(device).contiguous()
+            self._Y_dev = torch.as_tensor(self.outcomes_).to(device).contiguous()
+            self._keys_dev = None
+        return self._A_dev, self._Y_dev
+
+    def _keys_on(self, device, slot=True):
+        key = self._combine(self.slot_ if slot else None, self.cond_)
+        if key is None:
+            return None
+        if self._keys_dev is None or self._keys_dev.device != device:
+            self._keys_dev = torch.as_tensor(key).to(device)
+        return self._keys_dev
+
+    def _query_keys(self, dataset, idx, condition):
+        """The int32 key of every query window on the device (the slot column is read there: no host synchronisation), or
+        None when no rule is in use.  A window without a valid key gets -2, which no archive row carries."""
+        if self.cond_ is not None and condition is None:
+            raise ValueError("condition: the baseline was fitted with a condition, the query needs one too")
+        if self.cond_ is None and condition is not None:
+            raise ValueError("condition: the baseline was fitted without a condition")
+        if not self.same_slot and condition is None:
+            return None
+        origins = np.asarray([dataset.sample_indices[i] for i in idx], dtype=np.int64) + dataset.L_in
+        dev = dataset.X.device
+        key = torch.zeros(len(idx), device=dev, dtype=torch.int32)
+        if self.same_slot:
+            key = dataset.time_features[torch.as_tensor(origins).to(dev, non_blocking=True), 0].to(torch.int32)
+        if condition is not None:
+            cond = torch.as_tensor(self._condition_rows(condition, dataset, int(origins.max()) + 1)[origins]).to(dev, non_blocking=True)
+            key = torch.where(cond < 0, -2, cond * (SLOTS_PER_DAY if self.same_slot else 1) + key).to(torch.int32)
+        return key
+
+    def search_windows(self, dataset, indices: Sequence[int], condition=None):
+        """(idx (B, N, K) int32, dist (B, N, K) float32, count (B, N) int32) on the device for the windows `indices` of a
+        dataset of the fitted node count and L_out: `idx` are archive rows (add `row0_` for rows of the fitted dataset)."""
+        self._require_fitted()
+        T, Hh, W, Cc = dataset.X.shape
+        if Hh * W != self.num_nodes_:
+            raise ValueError(f"num_nodes: fitted on {self.num_nodes_} nodes, the dataset has {Hh * W}")
+        if dataset.L_out != self.H_:
+            raise ValueError(f"L_out: fitted for {self.H_} horizons, the dataset has L_out = {dataset.L_out}")
+        if dataset.L_in < self.match_len_:
+            raise ValueError(f"match_len: the fitted match length {self.match_len_} exceeds the dataset's L_in = {dataset.L_in}")
+        if not 0 <= self.channel < Cc:
+            raise ValueError(f"channel {self.channel} lies outside [0, {Cc})")
+        idx = [int(i) for i in indices]
+        for i in idx:
+            if not 0 <= i < dataset.num_samples:
+                raise IndexError(f"Index {i} is out of bounds for a dataset of size {dataset.num_samples}")
+        if not idx:
+            raise ValueError("search_windows() needs at least one window")
+        A, Y = self._archive_on(dataset.X.device)
+        key_arch = self._keys_on(A.device)
+        key_q = self._query_keys(dataset, idx, condition)
+        own = self._fit_ref is not None and self._fit_ref() is dataset
+        exclude = (self.match_len_ + self.H_ if self.exclude is None else self.exclude) if own else 0
+        starts = [dataset.sample_indices[i] for i in idx]
+        return analog_search(A, Y.shape[1], dataset.X.view(T, Hh * W, Cc), starts, dataset.L_in, dataset.L_out, self.match_len_,
+                             self.k, self.channel, key_arch, key_q, exclude, -self.row0_)
+
+    def _forecast(self, dataset, indices, condition, want_mean, want_members):
+        idx, _, count = self.search_windows(dataset, indices, condition)
+        return analog_forecast(self._Y_dev, idx, count, self.match_len_, self.H_, want_mean=want_mean, want_members=want_members) + (count,)
+
+    def members(self, dataset, indices: Sequence[int], condition=None) -> torch.Tensor:
+        """The K outcomes of every (window, node) as (K, B, L_out, N), the layout of `ensemble_members`: member k is what
+        followed the k-th nearest stretch; NaN where fewer than k + 1 stretches were admitted."""
+        return self._forecast(dataset, indices, condition, False, True)[1]
+
+    def forecast_windows(self, dataset, indices: Sequence[int], condition=None) -> torch.Tensor:
+        """The mean of the members as a (B, L_out, N, 1) device tensor, the layout of the model's output; NaN where no
+        stretch was admitted."""
+        return self._forecast(dataset, indices, condition, True, False)[0].unsqueeze(-1)
+
+    def predict(self, node_indices, steps: int) -> dict:
+        """{node: (steps,) float64}, steps <= the fitted L_out, for the nodes among `node_indices`: the forecast from the end
+        of the archive, whose last match_len rows are the query; the exclusion keeps it from finding itself.  With
+        `same_slot` the query's slot is the one after the archive's last row; a fitted condition is not applied."""
+        self._require_fitted()
+        if not 1 <= int(steps) <= self.H_:
+            raise ValueError(f"fitted for {self.H_} horizons, asked for {steps} steps")
+        A, Y = self._archive_on(self.device if self._A_dev is None else self._A_dev.device)
+        m, Ta = self.match_len_, A.shape[1]
+        tail = A[:, Ta - m:].t().contiguous().unsqueeze(-1)                 # (m, N, 1)
+        key_arch = key_q = None
+        if self.same_slot:
+            key_arch = torch.as_tensor(self.slot_).to(A.device)
+            key_q = torch.tensor([(int(self.slot_[Ta - 1]) + 1) % SLOTS_PER_DAY], dtype=torch.int32).to(A.device)
+        exclude = m + self.H_ if self.exclude is None else self.exclude
+        idx, _, count = analog_search(A, Y.shape[1], tail, [0], m, self.H_, m, self.k, 0, key_arch, key_q, exclude, Ta - m)
+        out = analog_forecast(Y, idx, count, m, self.H_)[0].cpu().numpy().astype(np.float64)
         return {int(n): out[0, :int(steps), int(n)] for n in node_indices if 0 <= int(n) < self.num_nodes_}
 
 

@@ -6,7 +6,8 @@ Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
                    input attribution, ensemble forecasts and their scores, spatial and temporal attention maps, conformal
                    prediction intervals, significance of the comparison (block bootstrap, Diebold-Mariano), event verification
                    (contingency scores, Brier, ROC, FSS), quantile forecasts (pinball-loss training, quantile scores,
-                   conformalized quantile regression), forecast combination (per-cell stacking weights), raw-data preprocessing
+                   conformalized quantile regression), forecast combination (per-cell stacking weights), the analog ensemble's
+                   probabilistic scores, raw-data preprocessing
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/features/    mirror of the reference's feature engineering (`from src.features.feature_engineering import ...`)
   src/data/        mirrors of the reference's dataset and data loader, and the series-backed SeriesWindowDataset
@@ -36,6 +37,9 @@ from .quantile import (CQRIntervals, QuantileModel, calibrate_cqr, evaluate_quan
                        quantile_forecast, write_quantiles)
 from . import combine  # noqa: F401
 from .combine import Combination, CombinationMoments, fit_combination, write_combination  # noqa: F401
+from . import analog  # noqa: F401
+from .analog import evaluate_analog_ensemble  # noqa: F401
+from .evaluate import ANALOG_NAME  # noqa: F401
 from . import preprocess  # noqa: F401
 from .preprocess import DeviceStandardScaler, preprocess_splits  # noqa: F401
 
@@ -50,4 +54,5 @@ __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradien
            "diebold_mariano", "evaluate_significance", "write_significance", "events", "EventThresholds", "target_slots",
            "evaluate_events", "write_events", "quantile", "PinballFn", "PinballLoss", "QuantileModel", "CQRIntervals",
            "quantile_config", "quantile_forecast", "evaluate_quantiles", "calibrate_cqr", "write_quantiles", "combine", "Combination",
-           "CombinationMoments", "fit_combination", "write_combination"]
+           "CombinationMoments", "fit_combination", "write_combination", "analog", "evaluate_analog_ensemble",
+           "ANALOG_NAME"]

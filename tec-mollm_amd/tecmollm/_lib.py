@@ -415,6 +415,30 @@ class TecmLinForecast(C.Structure):
     ]
 
 
+class TecmAnalogSearch(C.Structure):
+    _fields_ = [
+        ("A", c_f32p), ("Ta", C.c_int64), ("Ty", C.c_int64),
+        ("Xq", c_f32p), ("Tq", C.c_int64),
+        ("starts", C.c_void_p), ("starts_host_check", C.c_void_p),
+        ("origin_shift", C.c_int64),
+        ("N", C.c_int32), ("C", C.c_int32), ("channel", C.c_int32), ("L_in", C.c_int32), ("L_out", C.c_int32),
+        ("m", C.c_int32), ("K", C.c_int32), ("S", C.c_int32),
+        ("key_arch", C.c_void_p), ("Tk", C.c_int64), ("key_q", C.c_void_p),
+        ("exclude", C.c_int32), ("_pad", C.c_int32),
+        ("idx", C.c_void_p), ("dist", c_f32p), ("count", C.c_void_p),
+    ]
+
+
+class TecmAnalogForecast(C.Structure):
+    _fields_ = [
+        ("Y", c_f32p), ("Ty", C.c_int64),
+        ("idx", C.c_void_p), ("count", C.c_void_p),
+        ("N", C.c_int32), ("K", C.c_int32), ("m", C.c_int32), ("L_out", C.c_int32), ("B", C.c_int32), ("_pad", C.c_int32),
+        ("out", c_f32p), ("o_stride_b", C.c_int64), ("o_stride_h", C.c_int64), ("o_stride_n", C.c_int64),
+        ("members", c_f32p),
+    ]
+
+
 class TecmMoments(C.Structure):
     _fields_ = [
         ("src", C.c_void_p), ("rows", C.c_int64), ("cols", C.c_int64), ("ld", C.c_int64),
@@ -482,6 +506,7 @@ TECM_SAR_MAX_K, TECM_SAR_MAX_LAG, TECM_SAR_MAX_LONG_AR, TECM_SAR_MAX_OFFSET, TEC
 TECM_SAR_DEGENERATE, TECM_SAR_NONFINITE, TECM_SAR_MA_DROPPED = 1, 2, 4
 TECM_LIN_MAX_P, TECM_LIN_MAX_H, TECM_LIN_MAX_LAG, TECM_LIN_MAX_CHANNELS = 64, 32, 512, 8
 TECM_LIN_DEGENERATE, TECM_LIN_NONFINITE = 1, 2
+TECM_ANALOG_MAX_K, TECM_ANALOG_MAX_M, TECM_ANALOG_MAX_H = 32, 512, 32
 TECM_MOMENTS_MAX_BLOCKS = 2048
 TECM_FEATURES_MAX_CI = 15
 
@@ -608,6 +633,10 @@ EXPORTS = {
     "tecm_lin_gram": (C.c_int, [C.POINTER(TecmLinGram), C.c_void_p]),
     "tecm_lin_solve": (C.c_int, [C.POINTER(TecmLinSolve), C.c_void_p]),
     "tecm_lin_forecast": (C.c_int, [C.POINTER(TecmLinForecast), C.c_void_p]),
+    "tecm_analog_search_supported": (C.c_int, [C.POINTER(TecmAnalogSearch), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                               C.POINTER(C.c_int64)]),
+    "tecm_analog_search": (C.c_int, [C.POINTER(TecmAnalogSearch), C.c_void_p]),
+    "tecm_analog_forecast": (C.c_int, [C.POINTER(TecmAnalogForecast), C.c_void_p]),
     "tecm_moments_ws_bytes": (C.c_int64, [C.POINTER(TecmMoments)]),
     "tecm_moments": (C.c_int, [C.POINTER(TecmMoments), C.c_void_p]),
     "tecm_features_build": (C.c_int, [C.POINTER(TecmFeaturesBuild), C.c_void_p]),

@@ -52,7 +52,7 @@ def moment_index(members: int, a: int, b: int) -> int:
 
 def member_name(spec) -> str:
     """The name of one member: "model", a kind string of `window_baseline`, or the `baselines=` name of a fitted
-    `SarimaBaseline` / `LinearBaseline` ("SARIMA", "Linear")."""
+    `SarimaBaseline` / `LinearBaseline` / `AnalogBaseline` ("SARIMA", "Linear", "Analog")."""
     if isinstance(spec, str):
         if spec == MODEL_MEMBER or spec in KINDS:
             return spec
@@ -347,8 +347,8 @@ def fit_combination(model, dataset, edge_index, batch_size, members=(MODEL_MEMBE
     the combination is scored on): one `eval()` no-grad pass, the scoring pass of `evaluate_split` with one more launch per
     batch (`tecm_combine_moments`) and no host synchronisation, then one solve.
 
-    `members`: "model", the kind strings of `window_baseline`, fitted `SarimaBaseline` / `LinearBaseline` objects; at most
-    8, with unique names.  `groups` (one int32 id per dataset index, on the device) and `num_groups` fit one set of
+    `members`: "model", the kind strings of `window_baseline`, fitted `SarimaBaseline` / `LinearBaseline` / `AnalogBaseline`
+    objects; at most 8, with unique names.  `groups` (one int32 id per dataset index, on the device) and `num_groups` fit one set of
     coefficients per group, as `evaluate_maps` stratifies its scores.  `ridge`, `prior`, `pool` as in
     `CombinationMoments.fit`; `order` and `group` as in `evaluate_split` (the moments are summed over the ranks)."""
     specs = list(members)

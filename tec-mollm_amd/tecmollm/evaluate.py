@@ -37,21 +37,22 @@ NAMES = {"mean": "HistoricalAverage", "last": "Persistence", "periodic": "DayAgo
 MODEL_NAME = "TEC-MoLLM"
 SARIMA_NAME = "SARIMA"      # a fitted src.models.baselines.SarimaBaseline given as an element of `baselines=`
 LINEAR_NAME = "Linear"      # a fitted src.models.baselines.LinearBaseline, likewise
+ANALOG_NAME = "Analog"      # a fitted src.models.baselines.AnalogBaseline, likewise
 
 
 def baseline_name(kind) -> str:
-    """The result-dict name of one element of `baselines=`: a kind string of `KINDS`, a fitted `SarimaBaseline` or
-    `LinearBaseline`, or a fitted `tecmollm.combine.Combination` (its own `name`)."""
+    """The result-dict name of one element of `baselines=`: a kind string of `KINDS`, a fitted `SarimaBaseline`,
+    `LinearBaseline` or `AnalogBaseline`, or a fitted `tecmollm.combine.Combination` (its own `name`)."""
     if isinstance(kind, str):
         if kind in KINDS:
             return NAMES[kind]
     elif _is_combination(kind):
         return kind.name
     else:
-        from src.models.baselines import LinearBaseline, SarimaBaseline
-        for cls, name in ((SarimaBaseline, SARIMA_NAME), (LinearBaseline, LINEAR_NAME)):
+        from src.models.baselines import AnalogBaseline, LinearBaseline, SarimaBaseline
+        for cls, name in ((SarimaBaseline, SARIMA_NAME), (LinearBaseline, LINEAR_NAME), (AnalogBaseline, ANALOG_NAME)):
             if isinstance(kind, cls):
-                if kind.coef_ is None:
+                if (kind.n_candidates_ if cls is AnalogBaseline else kind.coef_) is None:
                     raise ValueError(f"a {cls.__name__} given as a baseline must be fitted")
                 return name
     raise ValueError(f"baselines must come from {sorted(KINDS)}, got {kind!r}")
@@ -193,7 +194,8 @@ def evaluate_split(model: torch.nn.Module, dataset, edge_index: torch.Tensor, ba
     One pass over the batches: the model's output and each baseline's stride-0 view are fed in place to a
     `HorizonMetrics` of their own, with no host synchronisation per batch.  An element of `baselines` is a kind string of
     `window_baseline`, a fitted `src.models.baselines.SarimaBaseline`, whose entry is named "SARIMA" (one
-    `tecm_sar_forecast` launch per batch), a fitted `LinearBaseline`, named "Linear" (one `tecm_lin_forecast` launch), or a
+    `tecm_sar_forecast` launch per batch), a fitted `LinearBaseline`, named "Linear" (one `tecm_lin_forecast` launch), a
+    fitted `AnalogBaseline`, named "Analog" (one `tecm_analog_search` and one `tecm_analog_forecast` launch per batch), or a
     fitted `tecmollm.combine.Combination`, named by its `name` (one `tecm_combine_apply` launch on the model's output and the
     member forecasts of the batch; one fitted with several groups needs `evaluate_maps`' groups); the same holds for `evaluate_maps` and `evaluate_ensemble`.  `order` and `group` as in `loop.validate`:
     a rank evaluates its shard and every rank returns the metrics of the whole split."""

@@ -1531,6 +1531,66 @@ typedef struct {
 } TecmCombineApply;
 int tecm_combine_apply(const TecmCombineApply* c, void* stream);
 
+/* (3m) multivariate scores of a K-member ensemble per (sample s, horizon h): the energy score and the variogram score
+ * (Scheuerer & Hamill 2015).  The scores of (3c) look at one cell at a time: permuting the members independently at every
+ * node leaves every one of them bit for bit the same.  These two look at the member as a MAP.
+ * Members and truth go through the value pipeline of (3c), unchanged (non-finite scaled member -> 0, inverse transform with two
+ * f32 roundings, nan_to_num, optional clip of the members only), which leaves float32 x_k[i], k < K, and y[i], i < I.
+ *
+ * Energy score -- everything after the pipeline is float64, ||.|| the Euclidean norm over the I nodes:
+ *   A = (1/K) sum_k ||x_k - y||      D = sum_{k<k'} ||x_k - x_k'||      E = ||mean_k x_k - y||    (the mean: k ascending, / K)
+ *   ES = A - D / K^2,  fair ES = A - D / (K (K - 1))  (NaN for K = 1), as the CRPS follows from A and D of (3c).  K = 1 is allowed:
+ *   ES of a point forecast is its Euclidean error E.
+ * Variogram score of order p, with f_p(d) = sqrt(d), d, d^2 for order = TECM_FIELD_ORDER_HALF / _ONE / _TWO (p = 0.5, 1, 2) --
+ * for every pair i < j whose class c = pair_class[i*I + j] is < NB:
+ *   v_o = f_p(|y_i - y_j|)      v_e = (sum_k f_p(|x_ki - x_kj|)) / K      e = v_o - v_e
+ *   in float32 (difference, square root to 1 ulp, the sum over k ascending, one division); e, e^2 and every sum over pairs,
+ *   samples or calls in float64.  Per (s, h, c): the number of pairs, sum e^2 (the score of the class), sum v_o and sum v_e
+ *   (the observed and the ensemble variogram: their ratio says whether the members are too smooth or too rough at that distance).
+ *   pair_class  (I, I) uint8 on the device, read only above the diagonal; a value >= NB excludes the pair.  NULL with NB = 0:
+ *               the energy score only.
+ * Outputs, ACCUMULATED across samples and calls:
+ *   es_stats (G, H, 4) doubles [n, sum A, sum D, sum E];   vs_stats (G, H, NB, 5) doubles [n, sum pairs, sum e^2, sum v_o, sum v_e]
+ * and, optional (NULL skips one), per sample and OVERWRITTEN: es_out (S, H, 3) doubles [A, D, E], vs_out (S, H, NB, 4) doubles
+ * [pairs, sum e^2, sum v_o, sum v_e]; the rows of a skipped sample are not written.
+ * Groups as in (3c): an id outside [0, G) skips the sample everywhere and sets TECM_BAD_GROUP in *err_flag; cells of a group
+ * that does not occur are neither read nor written.  members / target are addressed as in (3c) (element strides, read in
+ * place; node-contiguous is the coalesced layout).
+ * No atomics on the sums: blocks write partial sums to the workspace (tile pairs of T x T nodes for the variogram, up to
+ * TECM_FIELD_ENERGY_SPLITS node ranges for the norms), small kernels add them in a fixed order, and one thread per
+ * (g, h[, c]) adds the samples in ascending s -- two identical calls give identical bits.
+ * tecm_field_scores_plan is pure host arithmetic (no pointer is followed): 1 when the shape is served, with the node tile T,
+ * the dynamic LDS bytes of the largest kernel and the workspace bytes (each pointer may be NULL), else 0 with the reason
+ * in tecm_last_error.
+ * Limits: 1 <= K <= TECM_ENS_MAX_K, 0 <= NB <= TECM_FIELD_MAX_CLASSES, S and H <= TECM_FIELD_MAX_GRID, ceil(I / T) <=
+ * TECM_FIELD_MAX_TILES, scale != 0. */
+enum { TECM_FIELD_ORDER_HALF = 0, TECM_FIELD_ORDER_ONE = 1, TECM_FIELD_ORDER_TWO = 2 };
+#define TECM_FIELD_MAX_CLASSES 16
+#define TECM_FIELD_THREADS 256
+#define TECM_FIELD_ENERGY_SPLITS 8
+#define TECM_FIELD_MAX_GRID 65535
+#define TECM_FIELD_MAX_TILES 65535
+#define TECM_FIELD_ES_STATS 4
+#define TECM_FIELD_VS_STATS 5
+typedef struct {
+  const float* members; int64_t m_stride_k, m_stride_s, m_stride_h, m_stride_i;
+  const float* target; int64_t t_stride_s, t_stride_h, t_stride_i;
+  int64_t S; int32_t H; int32_t G; int64_t I;          /* samples, horizons, groups, nodes */
+  int32_t K; int32_t NB;                               /* members, pair classes */
+  double mean, scale;
+  float clip_lo, clip_hi; int32_t clip;
+  int32_t order;                                       /* TECM_FIELD_ORDER_* */
+  const uint8_t* pair_class;
+  double* es_stats; double* vs_stats;
+  double* es_out; double* vs_out;
+  const int32_t* group;
+  int32_t* err_flag;
+  void* workspace; int64_t workspace_bytes;
+} TecmFieldScores;
+int tecm_field_scores_plan(int64_t S, int32_t H, int64_t I, int32_t K, int32_t NB, int32_t* tile, int64_t* lds_bytes,
+                           int64_t* workspace_bytes);
+int tecm_field_scores(const TecmFieldScores* f, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

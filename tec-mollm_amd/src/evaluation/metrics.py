@@ -13,6 +13,8 @@ K-member ensemble per cell the same way (`tecm_ensemble_stats`: CRPS, spread, co
 Winkler score; `derive_intervals`); the intervals themselves come from `tecmollm/conformal.py`.  `EventMetrics` counts events
 per cell and threshold (`tecm_event_hist`, `tecm_event_fss`: contingency tables, the member histogram behind Brier / reliability
 / ROC, the sums of the fractions skill score; `derive_events`, `derive_fss`); thresholds and the pass are in `tecmollm/events.py`.
+`FieldMetrics` scores an ensemble's members as maps per (group, horizon) (`tecm_field_scores`: energy score, variogram score
+by class of node pairs; `derive_fields`); the class matrix and the files are in `tecmollm/fields.py`.
 
 Same numbers as the reference: inverse StandardScaler transform, non-finite guards, clip of predictions
 to [0, 200] TECU, MAE / RMSE / R^2 (sklearn semantics) / Pearson r per horizon and their averages.
@@ -886,3 +888,138 @@ class EventMetrics:
         out["thresholds"] = list(self.thresholds.labels)
         out["members"] = self.K
         return out
+
+
+# ------------------------------------------------------------------------------------ multivariate (field) scores
+FIELD_KEYS = ("count", "energy_score", "fair_energy_score", "field_error_mean", "pairs", "variogram_score",
+              "variogram_score_per_pair", "variogram_obs", "variogram_ens", "variogram_ratio")
+
+
+def derive_fields(es_stats: np.ndarray, vs_stats: np.ndarray, members: int) -> Dict[str, np.ndarray]:
+    """(..., 4) float64 sums [n, sum A, sum D, sum E] and (..., NB, 5) sums [n, sum pairs, sum e^2, sum v_o, sum v_e] (NB may
+    be 0) -> the FIELD_KEYS, NaN where nothing was seen:
+      energy_score = mean(A) - mean(D) / K^2        fair_energy_score = mean(A) - mean(D) / (K (K - 1))   (NaN for K = 1)
+      field_error_mean = mean(E), the Euclidean error of the ensemble-mean map (K = 1: equal to the energy score)
+      variogram_score = (sum e^2) / n, the score of a class per window     variogram_score_per_pair = (sum e^2) / pairs
+      variogram_obs, variogram_ens = (sum v_o) / pairs, (sum v_e) / pairs   variogram_ratio = variogram_ens / variogram_obs
+    (a ratio below 1: the members are smoother than the truth at that distance; above 1: rougher.)  "count" is n (...),
+    "pairs" the number of pairs counted (..., NB), over all windows."""
+    K = int(members)
+    es = np.asarray(es_stats, dtype=np.float64)
+    vs = np.asarray(vs_stats, dtype=np.float64)
+    if K < 1 or es.shape[-1] != _lib.TECM_FIELD_ES_STATS or vs.shape[-1] != _lib.TECM_FIELD_VS_STATS or vs.shape[:-2] != es.shape[:-1]:
+        raise ValueError(f"es_stats (..., 4) and vs_stats (..., NB, 5) do not fit (members {K}): {es.shape}, {vs.shape}")
+    n, sA, sD, sE = np.moveaxis(es, -1, 0)
+    nv, sp, se2, svo, sve = np.moveaxis(vs, -1, 0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        fair = (sA - sD / (K * (K - 1))) / n if K > 1 else np.full_like(n, np.nan)
+        out = {"count": n.copy(), "energy_score": (sA - sD / (K * K)) / n, "fair_energy_score": fair,
+               "field_error_mean": sE / n, "pairs": sp.copy(), "variogram_score": se2 / nv,
+               "variogram_score_per_pair": se2 / sp, "variogram_obs": svo / sp, "variogram_ens": sve / sp,
+               "variogram_ratio": sve / svo}
+    for k in ("energy_score", "fair_energy_score", "field_error_mean"):
+        out[k] = np.where(n == 0, np.nan, out[k])
+    out["variogram_score"] = np.where(nv == 0, np.nan, out["variogram_score"])
+    for k in ("variogram_score_per_pair", "variogram_obs", "variogram_ens", "variogram_ratio"):
+        out[k] = np.where(sp == 0, np.nan, out[k])
+    return out
+
+
+class FieldMetrics:
+    """Multivariate scores of a K-member ensemble per (group of the sample, horizon): the energy score and, with a class
+    matrix (`tecmollm.fields.pair_classes`), the variogram score of order 0.5, 1 or 2 per class of node pairs -- the scores
+    that see whether a member is a plausible map, which `EnsembleMetrics` cannot (it sorts the members of every cell).
+    update(members, true, groups) per batch on the device (`tecm_field_scores`: no host copy of the members, no atomics on
+    the sums, so the same batches give the same bits), compute() at the end.  members = 1 scores a point forecast's map."""
+
+    def __init__(self, num_horizons: int, num_nodes: int, members: int, pair_class: Optional[torch.Tensor] = None,
+                 num_classes: int = 0, order: float = 0.5, num_groups: int = 1, scaler=None,
+                 device: Union[str, torch.device] = "cuda"):
+        from tecmollm import ops
+        self.H, self.I, self.K, self.G, self.NB = int(num_horizons), int(num_nodes), int(members), int(num_groups), int(num_classes)
+        if min(self.H, self.I, self.G) < 1:
+            raise ValueError("FieldMetrics needs at least one horizon, one node and one group")
+        if not 1 <= self.K <= _lib.TECM_ENS_MAX_K:
+            raise ValueError(f"members must lie in [1, {_lib.TECM_ENS_MAX_K}], got {self.K}")
+        if not 0 <= self.NB <= _lib.TECM_FIELD_MAX_CLASSES:
+            raise ValueError(f"num_classes must lie in [0, {_lib.TECM_FIELD_MAX_CLASSES}], got {self.NB}")
+        if float(order) not in ops.FIELD_ORDERS:
+            raise ValueError(f"order must be one of {sorted(ops.FIELD_ORDERS)}, got {order}")
+        if (pair_class is None) != (self.NB == 0):
+            raise ValueError("pair_class and num_classes > 0 go together")
+        self.order = float(order)
+        self.pair_class = None
+        if pair_class is not None:
+            pc = torch.as_tensor(pair_class)
+            if pc.dtype != torch.uint8 or pc.shape != (self.I, self.I):
+                raise ValueError(f"pair_class must be a uint8 ({self.I}, {self.I}) matrix, got {pc.dtype} {tuple(pc.shape)}")
+            self.pair_class = pc.to(device).contiguous()
+        self.scaler = _scaler_params(scaler)
+        self.es_stats = torch.zeros(self.G, self.H, _lib.TECM_FIELD_ES_STATS, device=device, dtype=torch.float64)
+        self.vs_stats = torch.zeros(self.G, self.H, self.NB, _lib.TECM_FIELD_VS_STATS, device=device, dtype=torch.float64)
+        self._ws: Optional[torch.Tensor] = None
+
+    def reset(self) -> None:
+        self.es_stats.zero_()
+        self.vs_stats.zero_()
+
+    def update(self, members_scaled: torch.Tensor, y_true_scaled: torch.Tensor, groups: Optional[torch.Tensor] = None,
+               outputs=()) -> Dict[str, torch.Tensor]:
+        """members (K, S, H, N) or (K, S, H, N, 1) -- for members = 1 also a forecast (S, H, N[, 1]) -- and the truth (S, H, N)
+        or (S, H, N, 1), in scaled units and read in place whatever their strides; groups (S) int32 or None.  Returns the
+        per-sample tensors named in `outputs`, float64: "energy" (S, H, 3) = [A, D, E] and "variogram" (S, H, NB, 4) =
+        [pairs, sum e^2, sum v_o, sum v_e]; the rows of a sample with a bad group id are NaN."""
+        from tecmollm import devcheck, ops
+        t, S, H, I, ts, th, ti = _as_shi(y_true_scaled, "y_true")
+        m = members_scaled
+        _lib.require_gpu_tensor(m, "members")
+        if m.dim() == 5 and m.shape[-1] == 1:
+            m = m.squeeze(-1)
+        if self.K == 1 and m.dim() in (3, 4) and tuple(m.shape) != (1, S, H, I) and tuple(m.shape[:2]) == (S, H):
+            p, S2, H2, I2, ps, ph, pi = _as_shi(members_scaled, "y_pred")
+            m = p.as_strided((1, S2, H2, I2), (0, ps, ph, pi))
+        if m.dim() != 4:
+            raise ValueError(f"members must be (K, S, H, N), got {tuple(members_scaled.shape)}")
+        if tuple(m.shape) != (self.K, S, H, I) or H != self.H or I != self.I:
+            raise ValueError(f"shape mismatch: members {tuple(members_scaled.shape)}, true {tuple(y_true_scaled.shape)}, "
+                             f"expected members {self.K}, horizons {self.H}, nodes {self.I}")
+        if groups is not None:
+            _lib.require_gpu_tensor(groups, "groups", torch.int32)
+            if groups.shape != (S,):
+                raise ValueError(f"groups must hold one id per sample: {tuple(groups.shape)} for {S} samples")
+            groups = groups.contiguous()
+        unknown = set(outputs) - {"energy", "variogram"}
+        if unknown:
+            raise ValueError(f"outputs must come from ('energy', 'variogram'), got {sorted(unknown)}")
+        outs: Dict[str, torch.Tensor] = {}
+        if "energy" in outputs:
+            outs["energy"] = torch.full((S, H, 3), float("nan"), device=m.device, dtype=torch.float64)
+        if "variogram" in outputs:
+            outs["variogram"] = torch.full((S, H, self.NB, 4), float("nan"), device=m.device, dtype=torch.float64)
+        mean, scale = self.scaler if self.scaler is not None else (0.0, 1.0)
+        errs = devcheck.error_word(self.es_stats.device)
+        self._ws = ops.field_scores(m, t.as_strided((S, H, I), (ts, th, ti)), self.es_stats, self.vs_stats, self.pair_class,
+                                    order=self.order, mean=mean, scale=scale,
+                                    clip=(TEC_MIN, TEC_MAX) if self.scaler is not None else None, groups=groups,
+                                    err_flag=errs.ptr(), es_out=outs.get("energy"), vs_out=outs.get("variogram"),
+                                    workspace=self._ws)
+        if groups is not None:
+            errs.post()                        # only a group id can set the word here
+        return outs
+
+    def merge_(self, group=None) -> "FieldMetrics":
+        """Sum both statistics over the ranks of `group`, in place: they live in one buffer for the length of ONE
+        all-reduce.  See `HorizonMetrics.merge_`."""
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+            n = self.es_stats.numel()
+            flat = torch.cat([self.es_stats.reshape(-1), self.vs_stats.reshape(-1)])
+            dist.all_reduce(flat, op=dist.ReduceOp.SUM, group=group)
+            self.es_stats.copy_(flat[:n].view_as(self.es_stats))
+            self.vs_stats.copy_(flat[n:].view_as(self.vs_stats))
+        return self
+
+    def compute(self) -> Dict[str, object]:
+        """`derive_fields` of the statistics: the FIELD_KEYS as numpy arrays, (G, H) for the energy score and the count,
+        (G, H, NB) for the variogram keys and the pair counts; NaN where nothing was seen."""
+        return dict(derive_fields(self.es_stats.cpu().numpy(), self.vs_stats.cpu().numpy(), self.K))

@@ -439,6 +439,22 @@ class TecmAnalogForecast(C.Structure):
     ]
 
 
+class TecmFieldScores(C.Structure):
+    _fields_ = [
+        ("members", c_f32p), ("m_stride_k", C.c_int64), ("m_stride_s", C.c_int64), ("m_stride_h", C.c_int64),
+        ("m_stride_i", C.c_int64),
+        ("target", c_f32p), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64), ("t_stride_i", C.c_int64),
+        ("S", C.c_int64), ("H", C.c_int32), ("G", C.c_int32), ("I", C.c_int64),
+        ("K", C.c_int32), ("NB", C.c_int32),
+        ("mean", C.c_double), ("scale", C.c_double),
+        ("clip_lo", C.c_float), ("clip_hi", C.c_float), ("clip", C.c_int32), ("order", C.c_int32),
+        ("pair_class", C.c_void_p),
+        ("es_stats", C.c_void_p), ("vs_stats", C.c_void_p), ("es_out", C.c_void_p), ("vs_out", C.c_void_p),
+        ("group", C.c_void_p), ("err_flag", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+    ]
+
+
 class TecmMoments(C.Structure):
     _fields_ = [
         ("src", C.c_void_p), ("rows", C.c_int64), ("cols", C.c_int64), ("ld", C.c_int64),
@@ -508,6 +524,9 @@ TECM_LIN_MAX_P, TECM_LIN_MAX_H, TECM_LIN_MAX_LAG, TECM_LIN_MAX_CHANNELS = 64, 32
 TECM_LIN_DEGENERATE, TECM_LIN_NONFINITE = 1, 2
 TECM_ANALOG_MAX_K, TECM_ANALOG_MAX_M, TECM_ANALOG_MAX_H = 32, 512, 32
 TECM_MOMENTS_MAX_BLOCKS = 2048
+TECM_FIELD_ORDER_HALF, TECM_FIELD_ORDER_ONE, TECM_FIELD_ORDER_TWO = 0, 1, 2
+TECM_FIELD_MAX_CLASSES, TECM_FIELD_ES_STATS, TECM_FIELD_VS_STATS = 16, 4, 5
+TECM_FIELD_MAX_GRID, TECM_FIELD_MAX_TILES = 65535, 65535
 TECM_FEATURES_MAX_CI = 15
 
 
@@ -637,6 +656,9 @@ EXPORTS = {
                                                C.POINTER(C.c_int64)]),
     "tecm_analog_search": (C.c_int, [C.POINTER(TecmAnalogSearch), C.c_void_p]),
     "tecm_analog_forecast": (C.c_int, [C.POINTER(TecmAnalogForecast), C.c_void_p]),
+    "tecm_field_scores_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                         C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "tecm_field_scores": (C.c_int, [C.POINTER(TecmFieldScores), C.c_void_p]),
     "tecm_moments_ws_bytes": (C.c_int64, [C.POINTER(TecmMoments)]),
     "tecm_moments": (C.c_int, [C.POINTER(TecmMoments), C.c_void_p]),
     "tecm_features_build": (C.c_int, [C.POINTER(TecmFeaturesBuild), C.c_void_p]),

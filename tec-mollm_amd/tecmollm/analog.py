@@ -18,12 +18,15 @@ from .loop import _batches
 
 @torch.no_grad()
 def evaluate_analog_ensemble(analog, dataset, batch_size: int, scaler=None, trim: int = 1, groups: Optional[torch.Tensor] = None,
-                             num_groups: int = 1, condition=None, order: Optional[Sequence[int]] = None):
+                             num_groups: int = 1, condition=None, order: Optional[Sequence[int]] = None,
+                             fields=None):
     """Returns (results, maps, prob) as `evaluate_ensemble` does, with the single forecast "Analog": `results["Analog"]` is the
     `evaluate_horizons` dict of the members' mean -- bit for bit the entry `evaluate_split` gives the same fitted baseline at
     the same batch size --, `maps["Analog"]` its `MapMetrics.compute()`, and `prob` the `EnsembleMetrics.compute()` of the K
     members, which `write_ensemble` takes unchanged.  `groups` / `num_groups` as in `evaluate_maps`; `condition` as in
-    `AnalogBaseline.search_windows`.
+    `AnalogBaseline.search_windows`.  `fields` (a `tecmollm.fields.FieldSpec`) as in `evaluate_ensemble`: the members also
+    feed a `FieldMetrics`, whose keys are added to `prob` -- the analog members are matched per node, so this is where their
+    maps are judged; every other entry stays bit for bit the same.
 
     Every cell must have found its K analogs: a cell with fewer would put NaN members into the scores, so the pass keeps
     one flag on the device, reads it once at the end and raises ValueError if it is set (lower `k`, drop a condition, or
@@ -34,7 +37,7 @@ def evaluate_analog_ensemble(analog, dataset, batch_size: int, scaler=None, trim
         raise ValueError("evaluate_analog_ensemble() needs a fitted AnalogBaseline")
     if groups is not None and (groups.dtype != torch.int32 or groups.shape != (len(dataset),)):
         raise ValueError(f"groups must be an int32 tensor with one id per dataset index ({len(dataset)})")
-    hm = mm = em = short = None
+    hm = mm = em = fm = short = None
     for chunk in _batches(len(dataset), batch_size, order):
         y = dataset.batch(chunk)[2]
         idx, _, count = analog.search_windows(dataset, chunk, condition)
@@ -44,12 +47,16 @@ def evaluate_analog_ensemble(analog, dataset, batch_size: int, scaler=None, trim
             hm = HorizonMetrics(H, scaler, device=mean.device)
             mm = MapMetrics(H, N, int(num_groups), scaler, device=mean.device)
             em = EnsembleMetrics(H, N, analog.k, int(num_groups), scaler, trim, device=mean.device)
+            if fields is not None:
+                fm = fields.metrics(H, N, analog.k, int(num_groups), scaler, mean.device)
             short = torch.zeros((), device=mean.device, dtype=torch.bool)
         short |= (count < analog.k).any()
         ids = None
         if groups is not None:
             ids = groups[torch.as_tensor(chunk, dtype=torch.int64).to(groups.device, non_blocking=True)]
         em.update(members, y, ids)
+        if fm is not None:
+            fm.update(members, y, ids)
         pred = mean.unsqueeze(-1)
         hm.update(pred, y)
         mm.update(pred, y, ids)
@@ -60,5 +67,7 @@ def evaluate_analog_ensemble(analog, dataset, batch_size: int, scaler=None, trim
     results = {ANALOG_NAME: hm.merge_(None).compute()}
     maps = {ANALOG_NAME: mm.merge_(None).compute()}
     prob = em.merge_(None).compute()
+    if fm is not None:
+        prob.update(fields.entries(fm.merge_(None).compute()))
     check_device_errors(em.stats.device)
     return results, maps, prob

@@ -128,7 +128,7 @@ def evaluate_ensemble(model_or_models, dataset, edge_index: torch.Tensor, batch_
                       members: Optional[int] = 16, seed: int = 0, scaler=None, trim: int = 1,
                       baselines: Sequence[str] = ("mean",), groups: Optional[torch.Tensor] = None, num_groups: int = 1,
                       edge_weight: Optional[torch.Tensor] = None, order: Optional[Sequence[int]] = None, group=None,
-                      first_chunk: int = 0):
+                      first_chunk: int = 0, fields=None):
     """`evaluate_maps` plus the ensemble: returns (results, maps, prob).
 
     One pass over the batches.  Per batch: the deterministic `eval()` forward and the baselines, scored exactly as
@@ -137,7 +137,10 @@ def evaluate_ensemble(model_or_models, dataset, edge_index: torch.Tensor, batch_
     before its own, so that no two batches of a run share their masks and the shards add up to the single pass).  The ensemble-mean forecast (`mean_raw` of the kernel, scaled units) is
     scored like any other forecast under the name "TEC-MoLLM-MC", the last entry of `results` and `maps`; the members feed an
     `EnsembleMetrics`, whose `compute()` is `prob`.  With a sequence of models the deterministic entry is the first model's.
-    `groups`, `num_groups`, `order` and `group` as in `evaluate_maps`."""
+    `groups`, `num_groups`, `order` and `group` as in `evaluate_maps`.
+    `fields` (a `tecmollm.fields.FieldSpec`): the same members also feed a `FieldMetrics` -- the energy score and the variogram
+    score, which see the members as maps --, whose `compute()` keys (its sample count as "field_count") and `FieldSpec.describe()`
+    are added to `prob`; every other entry is bit for bit what the call without `fields` returns."""
     from src.evaluation.metrics import EnsembleMetrics, HorizonMetrics, MapMetrics
     if groups is not None and (groups.dtype != torch.int32 or groups.shape != (len(dataset),)):
         raise ValueError(f"groups must be an int32 tensor with one id per dataset index ({len(dataset)})")
@@ -149,7 +152,7 @@ def evaluate_ensemble(model_or_models, dataset, edge_index: torch.Tensor, batch_
     names = [MODEL_NAME] + base_names + [MC_NAME]
     hms: Dict[str, HorizonMetrics] = {}
     mms: Dict[str, MapMetrics] = {}
-    em = None
+    em = fm = None
     for ordinal, chunk in enumerate(_batches(len(dataset), batch_size, order)):
         x, tf, y = dataset.batch(chunk)
         first.eval()
@@ -160,11 +163,15 @@ def evaluate_ensemble(model_or_models, dataset, edge_index: torch.Tensor, batch_
                 hms[name] = HorizonMetrics(H, scaler, device=out.device)
                 mms[name] = MapMetrics(H, N, int(num_groups), scaler, device=out.device)
             em = EnsembleMetrics(H, N, K, int(num_groups), scaler, trim, device=out.device)
+            if fields is not None:
+                fm = fields.metrics(H, N, K, int(num_groups), scaler, out.device)
         ids = None
         if groups is not None:
             ids = groups[torch.as_tensor(chunk, dtype=torch.int64).to(groups.device, non_blocking=True)]
         mem = ensemble_members(model_or_models, x, tf, edge_index, members, seed, int(first_chunk) + ordinal, edge_weight)
         mean_raw = em.update(mem, y, ids, outputs=("mean_raw",))["mean_raw"]
+        if fm is not None:
+            fm.update(mem, y, ids)
         forecasts = batch_forecasts(dataset, chunk, out, base_names, kinds, ids)
         forecasts.append((MC_NAME, mean_raw.unsqueeze(-1)))
         for name, pred in forecasts:
@@ -175,6 +182,8 @@ def evaluate_ensemble(model_or_models, dataset, edge_index: torch.Tensor, batch_
     results = {name: hm.merge_(group).compute() for name, hm in hms.items()}
     maps = {name: mm.merge_(group).compute() for name, mm in mms.items()}
     prob = em.merge_(group).compute()
+    if fm is not None:
+        prob.update(fields.entries(fm.merge_(group).compute()))
     check_device_errors(em.stats.device)
     return results, maps, prob
 

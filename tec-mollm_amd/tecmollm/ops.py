@@ -976,6 +976,70 @@ def ensemble_stats(members: torch.Tensor, target: torch.Tensor, stats: torch.Ten
     check(lib().tecm_ensemble_stats(C.byref(e), stream_ptr()), "tecm_ensemble_stats")
 
 
+FIELD_ORDERS = {0.5: _lib.TECM_FIELD_ORDER_HALF, 1.0: _lib.TECM_FIELD_ORDER_ONE, 2.0: _lib.TECM_FIELD_ORDER_TWO}
+
+
+def field_scores_plan(S: int, H: int, I: int, K: int, NB: int) -> Tuple[int, int, int]:
+    """tecm_field_scores_plan: (node tile T, LDS bytes, workspace bytes) of one call with these sizes, as the library computes
+    them; TecmError with the library's reason for a shape it does not serve.  Host arithmetic only."""
+    tile, lds, ws = C.c_int32(0), C.c_int64(0), C.c_int64(0)
+    if not lib().tecm_field_scores_plan(int(S), int(H), int(I), int(K), int(NB), C.byref(tile), C.byref(lds), C.byref(ws)):
+        raise _lib.TecmError(lib().tecm_last_error().decode("utf-8", "replace"))
+    return tile.value, lds.value, ws.value
+
+
+def field_scores(members: torch.Tensor, target: torch.Tensor, es_stats: torch.Tensor, vs_stats: Optional[torch.Tensor],
+                 pair_class: Optional[torch.Tensor], *, order: float = 0.5, mean: float = 0.0, scale: float = 1.0,
+                 clip: Optional[Tuple[float, float]] = None, groups: Optional[torch.Tensor] = None, err_flag: int = 0,
+                 es_out: Optional[torch.Tensor] = None, vs_out: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """tecm_field_scores (include/tecmollm.h (3m)): one update of `es_stats` (G, H, 4) and `vs_stats` (G, H, NB, 5), float64,
+    from `members` (K, S, H, I) and `target` (S, H, I), float32 views of any strides, read in place.  `pair_class` is the
+    (I, I) uint8 class matrix (None: the energy score only, `vs_stats` is then not used); `order` 0.5, 1 or 2.  `es_out`
+    (S, H, 3) and `vs_out` (S, H, NB, 4), float64, take the per-sample sums.  `workspace` is a uint8 device tensor of at
+    least the plan's bytes (one is allocated when it is None or too small).  Returns the workspace used."""
+    K, S, H, I = members.shape
+    G = es_stats.shape[0]
+    if target.shape != (S, H, I):
+        raise ValueError(f"target must be (S, H, I) = {(S, H, I)}, got {tuple(target.shape)}")
+    if float(order) not in FIELD_ORDERS:
+        raise ValueError(f"order must be one of {sorted(FIELD_ORDERS)}, got {order}")
+    if es_stats.shape != (G, H, _lib.TECM_FIELD_ES_STATS) or es_stats.dtype != torch.float64 or not es_stats.is_contiguous():
+        raise ValueError(f"es_stats must be a contiguous float64 (G, {H}, {_lib.TECM_FIELD_ES_STATS}) tensor")
+    NB = 0
+    if pair_class is not None:
+        _lib.require_gpu_tensor(pair_class, "pair_class", torch.uint8)
+        if pair_class.shape != (I, I) or not pair_class.is_contiguous():
+            raise ValueError(f"pair_class must be a contiguous uint8 ({I}, {I}) tensor, got {tuple(pair_class.shape)}")
+        if vs_stats is None or vs_stats.dim() != 4:
+            raise ValueError("pair_class needs vs_stats (G, H, NB, 5)")
+        NB = vs_stats.shape[2]
+        if (vs_stats.shape != (G, H, NB, _lib.TECM_FIELD_VS_STATS) or vs_stats.dtype != torch.float64
+                or not vs_stats.is_contiguous()):
+            raise ValueError(f"vs_stats must be a contiguous float64 ({G}, {H}, NB, {_lib.TECM_FIELD_VS_STATS}) tensor")
+    for name, t, shape in (("es_out", es_out, (S, H, 3)), ("vs_out", vs_out, (S, H, NB, 4))):
+        if t is not None:
+            _lib.require_gpu_tensor(t, name, torch.float64)
+            if t.shape != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous float64 {shape} tensor, got {tuple(t.shape)}")
+    need = field_scores_plan(S, H, I, K, NB)[2]
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(max(need, 8), device=members.device, dtype=torch.uint8)
+    lo, hi = clip if clip is not None else (0.0, 0.0)
+    f = _lib.TecmFieldScores(members=members.data_ptr(), m_stride_k=members.stride(0), m_stride_s=members.stride(1),
+                             m_stride_h=members.stride(2), m_stride_i=members.stride(3),
+                             target=target.data_ptr(), t_stride_s=target.stride(0), t_stride_h=target.stride(1),
+                             t_stride_i=target.stride(2), S=S, H=H, G=G, I=I, K=K, NB=NB,
+                             mean=float(mean), scale=float(scale), clip_lo=lo, clip_hi=hi, clip=1 if clip is not None else 0,
+                             order=FIELD_ORDERS[float(order)], pair_class=ptr(pair_class) if NB else None,
+                             es_stats=es_stats.data_ptr(), vs_stats=ptr(vs_stats) if NB else None,
+                             es_out=ptr(es_out), vs_out=ptr(vs_out) if NB else None, group=ptr(groups),
+                             err_flag=err_flag or None, workspace=workspace.data_ptr(),
+                             workspace_bytes=workspace.numel() * workspace.element_size())
+    check(lib().tecm_field_scores(C.byref(f), stream_ptr()), "tecm_field_scores")
+    return workspace
+
+
 def _event_common(thr: torch.Tensor, thr_strides, dirs, slots, num_slots: int, S: int, H: int):
     _lib.require_gpu_tensor(thr, "thresholds", torch.float32)
     Q = len(dirs)

@@ -1591,6 +1591,45 @@ int tecm_field_scores_plan(int64_t S, int32_t H, int64_t I, int32_t K, int32_t N
                            int64_t* workspace_bytes);
 int tecm_field_scores(const TecmFieldScores* f, void* stream);
 
+/* (3n) reordering of ensemble members by a dependence template (ensemble copula coupling, Schefzik et al. 2013; the Schaake
+ * shuffle, Clark et al. 2004): what makes K calibrated values per cell into K maps.  It replaces the torch route -- two stable
+ * argsorts, a sort and take_along_dim on a materialised (K, S, H, I) template -- by one pass that reads 2 K floats and writes K
+ * floats per cell.  The scores of (3c) are unchanged by it, bit for bit; those of (3m) are what it is judged by.
+ * Per cell (s, h, i), under the total order "a before b":  a < b orders numbers;  equal numbers order by member index, lower
+ * first, and -0.0 equals +0.0;  a NaN comes after every number, NaNs among themselves by member index --
+ *   r_k            the position of template member k in that order, in [0, K)
+ *   v_(0..K-1)     the K values of the cell in that order
+ *   out[k,s,h,i] = v_(r_k)
+ * so the output holds exactly the cell's input values, bit patterns included (NaN payloads, the sign of a zero).  No value
+ * pipeline: the operands are compared as they are.
+ * values, the member template and out are addressed as base[k*stride_k + s*stride_s + h*stride_h + i*stride_i] (element strides,
+ * 64-bit, read and written in place; lanes run along the nodes, so stride_i == 1 is the coalesced layout).
+ * Template, one of
+ *   member tensor  rows == NULL: tmpl is (K, S, H, I) with t_stride_k/s/h/i.
+ *   dated rows     rows != NULL, (S, K) int32 on the device, contiguous: tmpl is a series of T rows and
+ *                  template[k,s,h,i] = tmpl[(rows[s*K + k] + h)*t_stride_row + i*t_stride_i]   (t_stride_k/s/h are not used),
+ *                  read in place: a (T, I) series has t_stride_row = I, t_stride_i = 1, a node-major (I, T) one t_stride_row = 1,
+ *                  t_stride_i = T.  A sample with rows[s*K + k] < 0 or rows[s*K + k] + H > T for any k reads nothing of the
+ *                  series: every out[., s, ., .] is NaN, every out_rank[., s, ., .] is 255, and TECM_BAD_ROW is set in
+ *                  *err_flag (the sticky device error word of (3b); never NULL with rows).  Nothing is clamped.
+ * out_rank (optional, NULL skips it): (K, S, H, I) uint8, contiguous, r_k.
+ * Aliasing: out may be the very view values is (same pointer, same four strides): the owner of a cell reads its K values before
+ * it writes them.  Every other overlap of out or out_rank with an operand (compared by the byte ranges the strides span) is
+ * TECM_E_ARG, and so is a zero stride of out along an axis longer than 1.
+ * One wave per (tile of 64 nodes, h, s); K is served by the compile-time bucket 2, 4, 8, 16, 32 or 64 >= K, as in (3c).
+ * Limits: 2 <= K <= TECM_ENS_MAX_K, S and H <= TECM_REORDER_MAX_GRID, with rows T >= H. */
+#define TECM_REORDER_MAX_GRID 65535
+typedef struct {
+  const float* values; int64_t v_stride_k, v_stride_s, v_stride_h, v_stride_i;
+  const float* tmpl; int64_t t_stride_k, t_stride_s, t_stride_h, t_stride_i;
+  const int32_t* rows; int64_t t_stride_row; int64_t T;  /* dated template only */
+  float* out; int64_t o_stride_k, o_stride_s, o_stride_h, o_stride_i;
+  uint8_t* out_rank;
+  int64_t S; int32_t H; int32_t K; int64_t I;          /* samples, horizons, members, nodes */
+  int32_t* err_flag;
+} TecmMemberReorder;
+int tecm_member_reorder(const TecmMemberReorder* r, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -897,10 +897,15 @@ class AnalogBaseline:
         idx, _, count = self.search_windows(dataset, indices, condition)
         return analog_forecast(self._Y_dev, idx, count, self.match_len_, self.H_, want_mean=want_mean, want_members=want_members) + (count,)
 
-    def members(self, dataset, indices: Sequence[int], condition=None) -> torch.Tensor:
+    def members(self, dataset, indices: Sequence[int], condition=None, reorder=None) -> torch.Tensor:
         """The K outcomes of every (window, node) as (K, B, L_out, N), the layout of `ensemble_members`: member k is what
-        followed the k-th nearest stretch; NaN where fewer than k + 1 stretches were admitted."""
-        return self._forecast(dataset, indices, condition, False, True)[1]
+        followed the k-th nearest stretch; NaN where fewer than k + 1 stretches were admitted.  `reorder` (a template of
+        `tecmollm.coherence`): the members of every cell are handed to the member indices in the template's rank order, in
+        place -- member k is then a map and no longer the k-th nearest; NaNs go to the template's highest ranks."""
+        members = self._forecast(dataset, indices, condition, False, True)[1]
+        if reorder is not None:
+            reorder.apply_(members, dataset, indices)
+        return members
 
     def forecast_windows(self, dataset, indices: Sequence[int], condition=None) -> torch.Tensor:
         """The mean of the members as a (B, L_out, N, 1) device tensor, the layout of the model's output; NaN where no

@@ -7,7 +7,8 @@ Package layout (inside `tec-mollm_amd/`, which must be on sys.path):
                    prediction intervals, significance of the comparison (block bootstrap, Diebold-Mariano), event verification
                    (contingency scores, Brier, ROC, FSS), quantile forecasts (pinball-loss training, quantile scores,
                    conformalized quantile regression), forecast combination (per-cell stacking weights), the analog ensemble's
-                   probabilistic scores, multivariate ensemble scores (energy and variogram score), raw-data preprocessing
+                   probabilistic scores, multivariate ensemble scores (energy and variogram score), coherent ensemble maps (ECC and
+                   Schaake-shuffle reordering), raw-data preprocessing
   src/model/       mirror of the reference's module API (`from src.model.tec_mollm import TEC_MoLLM`)
   src/features/    mirror of the reference's feature engineering (`from src.features.feature_engineering import ...`)
   src/data/        mirrors of the reference's dataset and data loader, and the series-backed SeriesWindowDataset
@@ -42,6 +43,9 @@ from .analog import evaluate_analog_ensemble  # noqa: F401
 from .evaluate import ANALOG_NAME  # noqa: F401
 from . import fields  # noqa: F401
 from .fields import FieldSpec, grid_pair_classes, pair_classes, write_fields  # noqa: F401
+from . import coherence  # noqa: F401
+from .coherence import (EccTemplate, SchaakeTemplate, evaluate_quantile_ensemble, quantile_members,  # noqa: F401
+                        reorder_members)
 from . import preprocess  # noqa: F401
 from .preprocess import DeviceStandardScaler, preprocess_splits  # noqa: F401
 
@@ -57,4 +61,5 @@ __all__ = ["LIB_PATH", "TecmError", "lib", "check_device_errors", "input_gradien
            "evaluate_events", "write_events", "quantile", "PinballFn", "PinballLoss", "QuantileModel", "CQRIntervals",
            "quantile_config", "quantile_forecast", "evaluate_quantiles", "calibrate_cqr", "write_quantiles", "combine", "Combination",
            "CombinationMoments", "fit_combination", "write_combination", "analog", "evaluate_analog_ensemble",
-           "ANALOG_NAME", "fields", "FieldSpec", "pair_classes", "grid_pair_classes", "write_fields"]
+           "ANALOG_NAME", "fields", "FieldSpec", "pair_classes", "grid_pair_classes", "write_fields",
+           "coherence", "reorder_members", "SchaakeTemplate", "EccTemplate", "quantile_members", "evaluate_quantile_ensemble"]

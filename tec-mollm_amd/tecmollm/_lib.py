@@ -455,6 +455,21 @@ class TecmFieldScores(C.Structure):
     ]
 
 
+class TecmMemberReorder(C.Structure):
+    _fields_ = [
+        ("values", c_f32p), ("v_stride_k", C.c_int64), ("v_stride_s", C.c_int64), ("v_stride_h", C.c_int64),
+        ("v_stride_i", C.c_int64),
+        ("tmpl", c_f32p), ("t_stride_k", C.c_int64), ("t_stride_s", C.c_int64), ("t_stride_h", C.c_int64),
+        ("t_stride_i", C.c_int64),
+        ("rows", C.c_void_p), ("t_stride_row", C.c_int64), ("T", C.c_int64),
+        ("out", c_f32p), ("o_stride_k", C.c_int64), ("o_stride_s", C.c_int64), ("o_stride_h", C.c_int64),
+        ("o_stride_i", C.c_int64),
+        ("out_rank", C.c_void_p),
+        ("S", C.c_int64), ("H", C.c_int32), ("K", C.c_int32), ("I", C.c_int64),
+        ("err_flag", C.c_void_p),
+    ]
+
+
 class TecmMoments(C.Structure):
     _fields_ = [
         ("src", C.c_void_p), ("rows", C.c_int64), ("cols", C.c_int64), ("ld", C.c_int64),
@@ -527,6 +542,7 @@ TECM_MOMENTS_MAX_BLOCKS = 2048
 TECM_FIELD_ORDER_HALF, TECM_FIELD_ORDER_ONE, TECM_FIELD_ORDER_TWO = 0, 1, 2
 TECM_FIELD_MAX_CLASSES, TECM_FIELD_ES_STATS, TECM_FIELD_VS_STATS = 16, 4, 5
 TECM_FIELD_MAX_GRID, TECM_FIELD_MAX_TILES = 65535, 65535
+TECM_REORDER_MAX_GRID = 65535
 TECM_FEATURES_MAX_CI = 15
 
 
@@ -659,6 +675,7 @@ EXPORTS = {
     "tecm_field_scores_plan": (C.c_int, [C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "tecm_field_scores": (C.c_int, [C.POINTER(TecmFieldScores), C.c_void_p]),
+    "tecm_member_reorder": (C.c_int, [C.POINTER(TecmMemberReorder), C.c_void_p]),
     "tecm_moments_ws_bytes": (C.c_int64, [C.POINTER(TecmMoments)]),
     "tecm_moments": (C.c_int, [C.POINTER(TecmMoments), C.c_void_p]),
     "tecm_features_build": (C.c_int, [C.POINTER(TecmFeaturesBuild), C.c_void_p]),

@@ -19,7 +19,7 @@ from .loop import _batches
 @torch.no_grad()
 def evaluate_analog_ensemble(analog, dataset, batch_size: int, scaler=None, trim: int = 1, groups: Optional[torch.Tensor] = None,
                              num_groups: int = 1, condition=None, order: Optional[Sequence[int]] = None,
-                             fields=None):
+                             fields=None, reorder=None):
     """Returns (results, maps, prob) as `evaluate_ensemble` does, with the single forecast "Analog": `results["Analog"]` is the
     `evaluate_horizons` dict of the members' mean -- bit for bit the entry `evaluate_split` gives the same fitted baseline at
     the same batch size --, `maps["Analog"]` its `MapMetrics.compute()`, and `prob` the `EnsembleMetrics.compute()` of the K
@@ -27,6 +27,10 @@ def evaluate_analog_ensemble(analog, dataset, batch_size: int, scaler=None, trim
     `AnalogBaseline.search_windows`.  `fields` (a `tecmollm.fields.FieldSpec`) as in `evaluate_ensemble`: the members also
     feed a `FieldMetrics`, whose keys are added to `prob` -- the analog members are matched per node, so this is where their
     maps are judged; every other entry stays bit for bit the same.
+    `reorder` (a `tecmollm.coherence.SchaakeTemplate`, or an `EccTemplate` built with its `edge_index`): the members of every
+    batch are reordered in place by the template before they are scored, which makes maps of them.  The mean forecast is
+    taken before that, and the per-cell scores sort each cell's members: `results`, `maps` and every per-cell entry of
+    `prob` stay bit for bit the same, the field entries change.  None: nothing is reordered.
 
     Every cell must have found its K analogs: a cell with fewer would put NaN members into the scores, so the pass keeps
     one flag on the device, reads it once at the end and raises ValueError if it is set (lower `k`, drop a condition, or
@@ -38,7 +42,7 @@ def evaluate_analog_ensemble(analog, dataset, batch_size: int, scaler=None, trim
     if groups is not None and (groups.dtype != torch.int32 or groups.shape != (len(dataset),)):
         raise ValueError(f"groups must be an int32 tensor with one id per dataset index ({len(dataset)})")
     hm = mm = em = fm = short = None
-    for chunk in _batches(len(dataset), batch_size, order):
+    for ordinal, chunk in enumerate(_batches(len(dataset), batch_size, order)):
         y = dataset.batch(chunk)[2]
         idx, _, count = analog.search_windows(dataset, chunk, condition)
         mean, members = analog_forecast(analog._Y_dev, idx, count, analog.match_len_, analog.H_, want_members=True)
@@ -51,6 +55,8 @@ def evaluate_analog_ensemble(analog, dataset, batch_size: int, scaler=None, trim
                 fm = fields.metrics(H, N, analog.k, int(num_groups), scaler, mean.device)
             short = torch.zeros((), device=mean.device, dtype=torch.bool)
         short |= (count < analog.k).any()
+        if reorder is not None:
+            reorder.apply_(members, dataset, chunk, chunk=ordinal)
         ids = None
         if groups is not None:
             ids = groups[torch.as_tensor(chunk, dtype=torch.int64).to(groups.device, non_blocking=True)]

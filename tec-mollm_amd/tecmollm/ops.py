@@ -1040,6 +1040,27 @@ def field_scores(members: torch.Tensor, target: torch.Tensor, es_stats: torch.Te
     return workspace
 
 
+def member_reorder(values: torch.Tensor, template: torch.Tensor, out: torch.Tensor, rows: Optional[torch.Tensor] = None,
+                   out_rank: Optional[torch.Tensor] = None, err_flag: int = 0) -> None:
+    """tecm_member_reorder (include/tecmollm.h (3n)): `out[k, s, h, i]` = the value of cell (s, h, i) whose position among the
+    cell's K `values` is the position of `template[k, s, h, i]` among the cell's K template values.  `values` and `out`
+    (K, S, H, I) float32 views of any strides (`out` may be `values` itself); `template` a (K, S, H, I) view, or with `rows`
+    (S, K) int32 contiguous a (T, I) series view whose rows `rows[s, k] + h` are the template; `out_rank` a contiguous uint8
+    (K, S, H, I) tensor.  `err_flag` is the address of the device error word, needed with `rows`.  Shapes and dtypes are the
+    caller's to check (`tecmollm.coherence.reorder_members` does)."""
+    K, S, H, I = values.shape
+    r = _lib.TecmMemberReorder(values=values.data_ptr(), v_stride_k=values.stride(0), v_stride_s=values.stride(1),
+                               v_stride_h=values.stride(2), v_stride_i=values.stride(3),
+                               tmpl=template.data_ptr(), out=out.data_ptr(), o_stride_k=out.stride(0),
+                               o_stride_s=out.stride(1), o_stride_h=out.stride(2), o_stride_i=out.stride(3),
+                               out_rank=ptr(out_rank), S=S, H=H, K=K, I=I, err_flag=err_flag or None)
+    if rows is None:
+        r.t_stride_k, r.t_stride_s, r.t_stride_h, r.t_stride_i = template.stride()
+    else:
+        r.rows, r.T, r.t_stride_row, r.t_stride_i = rows.data_ptr(), template.shape[0], template.stride(0), template.stride(1)
+    check(lib().tecm_member_reorder(C.byref(r), stream_ptr()), "tecm_member_reorder")
+
+
 def _event_common(thr: torch.Tensor, thr_strides, dirs, slots, num_slots: int, S: int, H: int):
     _lib.require_gpu_tensor(thr, "thresholds", torch.float32)
     Q = len(dirs)
